@@ -8,9 +8,14 @@ is one 2-layer GMM graph, N=1000, generator seed 0 (mdcommunity_amd.gmm reproduc
 reference's U/GMM.py graph for that seed), unit-cost checkpoint g0.5 iter 100000; with
 --gpus N every rank (one process per GPU) runs its own replica (weak scaling).
 
-The same run also measures the batched path (configs[2]: 256 graphs N=1000 per GPU, seeds
-sharded contiguously over ranks, per-graph AUDC gathered over RCCL: configs[4]'s shape at
---gpus 8 --batch-graphs 512) as the "batch" object.
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the
+last step's outputs when `--dump-outputs DIR` is given and prints the line; everything below
+that is not the headline runs only with `--full`.
+
+With `--full` the same run also measures the batched path (configs[2]: 256 graphs N=1000 per
+GPU, seeds sharded contiguously over ranks, per-graph AUDC gathered over RCCL: configs[4]'s
+shape at --gpus 8 --batch-graphs 512) as the "batch" object, the C5, degree-cost and
+testReal-sized objects, the PCIe-inclusive and per-step-protocol rates, the golden comparison.
 
 Ranks: under torchrun (WORLD_SIZE set) this process is one rank.  Otherwise `--gpus N` (N > 1)
 makes this process a launcher: it spawns N rank processes of this script (RANK / LOCAL_RANK /
@@ -19,10 +24,10 @@ line and exits with the worst rank's status.  `--cpu-dry-run` runs the same laun
 shard / gather code on the CPU (gloo, a host stub in place of the device engine): the plumbing
 check of tests/test_parallel.py.
 
-Prints one JSON line (rank 0) with the roofline of the rollout kernel (HIP-event device time
-of every launch in the timed region, algorithmic flops / bytes from the device's own
-per-prediction trace) and the CPU baseline (the oracle, a reference-shaped
-restatement, timed on this host's cores on a bounded sample).
+Prints one JSON line (rank 0); with `--full` it carries the roofline of the rollout kernel
+(HIP-event device time of every launch in the timed region, algorithmic flops / bytes from the
+device's own per-prediction trace) and the CPU baseline (the oracle, a
+reference-shaped restatement, timed on this host's cores on a bounded sample).
 """
 import argparse
 import hashlib
@@ -47,6 +52,10 @@ KERNEL_SOURCES = ["mdcommunity_amd/csrc/md_kernels.hip", "mdcommunity_amd/csrc/m
                   "mdcommunity_amd/csrc/md_common.h", "mdcommunity_amd/csrc/md_abi.cpp",
                   "mdcommunity_amd/csrc/md_wave.h"]
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic.json")
+# keys of the result line that only a --full run measures or checks
+FULL_ONLY = ("dist_check", "audc_match", "seq_prefix_match", "seq_certified_match", "predictions_per_step",
+             "pcie_inclusive_value", "per_step_protocol_value", "per_step_protocol_same_sequence", "roofline",
+             "batch", "c5", "degree", "real_scale")
 
 
 def step_flops(n, m0, m1, g=1):
@@ -75,6 +84,14 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else of the line: roofline, golden "
+                         "comparison, PCIe-inclusive and per-step-protocol rates, the batch, C5, degree-cost and "
+                         "testReal-sized objects, the collectives check and the CPU baselines (the options below "
+                         "that size or skip those take effect only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (removal sequence, LMCC ranks, max_rank of the "
+                         "headline graph) as DIR/<name>.npy (float64), after the timed steps")
     ap.add_argument("--batch-graphs", type=int, default=256, help="graphs per GPU of the batch object (0: skip)")
     ap.add_argument("--batch-steps", type=int, default=2)
     ap.add_argument("--degree-steps", type=int, default=3, help="timed degree-cost rollouts (0: skip)")
@@ -106,7 +123,10 @@ def parse(argv=None):
                     help="N > 1 ranks on fewer GPUs (rank r on GPU r mod the visible count, gloo for the "
                          "collectives): the multi-rank path with the real engine on a one-GPU box; not a "
                          "scaling measurement (the line says so)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs is not None and args.steps <= 0:
+        ap.error("--dump-outputs writes the last timed step's outputs: it needs --steps > 0")
+    return args
 
 
 # ------------------------------------------------------------------ launcher (no GPU calls here)
@@ -360,6 +380,19 @@ def run_steps(eng, steps):
         removals += sum(len(o[0]) for o in outs)
         last = (eng.max_rank(), outs)
     return kernel_ms, launches, removals, last, s0_ms
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: what a caller of the timed path receives from its last step, one float64
+    .npy per array (the values are int32, exact in float64): the headline graph's removal
+    sequence and the LMCC rank after each removal (Engine.rollout), and max_rank
+    (Engine.max_rank).  The inputs are fixed by --n / --seed, so two builds run with the same
+    arguments can be compared file by file."""
+    mr, outs = last
+    seq, ranks = outs[0]
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("seq", seq), ("ranks", ranks), ("max_rank", mr)):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float64))
 
 
 def trace_work(eng, n_graphs):
@@ -701,6 +734,7 @@ def rank_main(args):
         def make_engine(weights, cost_mode=_lib.MD_COST_UNIT):
             return _lib.Engine(weights, device=gpu, cost_mode=cost_mode)
 
+    full = args.full
     graphs_of = _graph_source(args, gpu)
     weights = engine.load_weights(engine.DEFAULT_UNIT)
     eng = make_engine(weights)
@@ -726,14 +760,17 @@ def rank_main(args):
         kernel_ms, launches, removals, last, s0_ms = run_steps(eng, args.steps)
         sync()
         elapsed = time.perf_counter() - t0
-        F, B = trace_work(eng, 1)
+        if full:
+            F, B = trace_work(eng, 1)
         mr, outs = last
         seq, ranks = outs[0]
         audc = audc_of(ranks, mr[0], args.n)
+        if rank == 0 and args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, last)
     # host-buffer-inclusive rate (edge lists uploaded over PCIe by md_load_graphs, sequences
     # read back): reported beside `value`, never as it (Measurement)
     pcie_rate = None
-    if args.steps > 0 and not args.cpu_dry_run:
+    if full and args.steps > 0 and not args.cpu_dry_run:
         tp = time.perf_counter()
         prem = 0
         for _ in range(3):
@@ -744,7 +781,7 @@ def rank_main(args):
     # the same rollouts with the K2 end-game shortcut off (every removal step runs its forward
     # pass and, on a tie, its own host hand-shake; MD_VARIANT bit 2048): reported beside `value`
     per_step_rate = per_step_same = None
-    if args.steps > 0 and not args.no_per_step and not args.cpu_dry_run:
+    if full and args.steps > 0 and not args.no_per_step and not args.cpu_dry_run:
         old_v = os.environ.get("MD_VARIANT")
         os.environ["MD_VARIANT"] = str(int(old_v or "0") | 2048)
         try:
@@ -768,7 +805,7 @@ def rank_main(args):
 
     # ---------------- batch object (configs[2]: batch_graphs per GPU, weak-scaled over ranks)
     batch = None
-    if args.batch_graphs > 0:
+    if full and args.batch_graphs > 0:
         total = args.batch_graphs * world
         lo, hi = parallel.shard(total, rank, world)
         batch, baudc, brem = many_graph_object(args, "batch", graphs_of(range(lo, hi)), lo, args.batch_steps, rank,
@@ -783,7 +820,7 @@ def rank_main(args):
     # ---------------- C5 object (configs[4]): the same c5_graphs graphs at every world size,
     # split contiguously over the ranks (strong scaling); one RCCL all-gather of AUDC + counts
     c5 = None
-    if args.c5_graphs > 0:
+    if full and args.c5_graphs > 0:
         lo, hi = parallel.shard(args.c5_graphs, rank, world)
         c5, caudc, crem = many_graph_object(args, "c5", graphs_of(range(lo, hi)), lo, args.c5_steps, rank, world,
                                             dist, dev, make_engine, weights, sync, parallel)
@@ -813,17 +850,17 @@ def rank_main(args):
     # ---------------- degree-cost variant (configs[3] shape: the D/ agent on a synthetic N=1000
     # multiplex, the GMM seed-0 graph; real testReal inputs are absent), single graph, rank 0
     degree = None
-    if rank == 0 and args.degree_steps > 0 and not args.cpu_dry_run:
+    if full and rank == 0 and args.degree_steps > 0 and not args.cpu_dry_run:
         degree = degree_object(args, edges, make_engine)
     real = None
-    if rank == 0 and args.real_steps > 0 and not args.cpu_dry_run:
+    if full and rank == 0 and args.real_steps > 0 and not args.cpu_dry_run:
         import tempfile
         with tempfile.TemporaryDirectory() as td:
             real = real_scale_object(args, make_engine, td)
 
     # the collectives themselves, checked: a gather of known per-rank data must come back whole
     dist_check = None
-    if dist is not None:
+    if full and dist is not None:
         blk = parallel.shard(64, rank, world)
         ga, gr = parallel.gather_results(dist, [float(i) + 0.5 for i in range(*blk)], list(range(*blk)), dev)
         dist_check = dict(backend=backend, world=dist.get_world_size(),
@@ -833,11 +870,11 @@ def rank_main(args):
         golden = None
         gpath = os.path.join(ROOT, "tests", "golden", f"rollout_gmm1000_s{args.seed}.npz")
         cpath = os.path.join(ROOT, "tests", "golden", f"cert_gmm1000_s{args.seed}.npz")
-        if args.n == 1000 and os.path.exists(gpath) and os.path.exists(cpath):
+        if full and args.n == 1000 and os.path.exists(gpath) and os.path.exists(cpath):
             with np.load(gpath) as z, np.load(cpath) as c:
                 golden = dict(audc=float(z["score"]), seq=z["seq"].tolist(), cert=c["gpu_seq"].tolist(),
                               prefix=int(c["prefix"]))
-        traffic, traffic_note = load_traffic()
+        traffic, traffic_note = load_traffic() if full else (None, "not read")
         if batch is not None and traffic is not None and args.batch_graphs == 256 and "batch" in traffic:
             apply_traffic(batch["roofline"], traffic["batch"], batch["roofline"]["launches_per_step"])
             batch["roofline"]["traffic_note"] = traffic_note
@@ -849,11 +886,13 @@ def rank_main(args):
         if have:
             while k < min(len(seq), len(golden["seq"])) and seq[k] == golden["seq"][k]:
                 k += 1
-        rl = roofline(F, B, kernel_ms / max(1, args.steps), launches / max(1, args.steps),
-                      traffic.get("hbm_bytes_per_launch") if traffic else None)
-        rl["traffic_note"] = traffic_note
-        if traffic:
-            rl["mfma_busy"] = traffic.get("mfma_busy")
+        rl = None
+        if full:
+            rl = roofline(F, B, kernel_ms / max(1, args.steps), launches / max(1, args.steps),
+                          traffic.get("hbm_bytes_per_launch") if traffic else None)
+            rl["traffic_note"] = traffic_note
+            if traffic:
+                rl["mfma_busy"] = traffic.get("mfma_busy")
         line = {
             "metric": METRIC,
             "value": tot_removals / max_elapsed,
@@ -907,8 +946,13 @@ def rank_main(args):
             "real_scale": real,
             "kernel_src_hash": kernel_src_hash(),
         }
-        line["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline and args.steps > 0 and not args.cpu_dry_run:
+        line["full"] = full
+        if not full:
+            for key in FULL_ONLY:  # not measured in a plain run: left out rather than reported as null
+                del line[key]
+        else:
+            line["cpu_baseline"] = None
+        if full and world == 1 and not args.no_cpu_baseline and args.steps > 0 and not args.cpu_dry_run:
             cb = cpu_baseline(edges, args.n, args.cpu_sample_seconds)
             line["cpu_baseline"] = cb
             line["vs_cpu_baseline"] = line["value"] / cb["value"]

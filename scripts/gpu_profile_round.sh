@@ -19,12 +19,12 @@ R=$(pwd)
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-SINGLE="--batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0"
-BATCH="--steps 0 --batch-graphs 256 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0"
-C5="--steps 0 --batch-graphs 0 --c5-graphs 4096 --c5-steps 1 --c5-shard-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0"
-DEGREE="--steps 0 --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 2 --no-per-step --real-steps 0"
-REAL_DEGREE="--steps 0 --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 1 --real-cases degree"
-REAL_UNIT="--steps 0 --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 1 --real-cases unit"
+SINGLE="--full --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0"
+BATCH="--full --steps 0 --batch-graphs 256 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0"
+C5="--full --steps 0 --batch-graphs 0 --c5-graphs 4096 --c5-steps 1 --c5-shard-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0"
+DEGREE="--full --steps 0 --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 2 --no-per-step --real-steps 0"
+REAL_DEGREE="--full --steps 0 --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 1 --real-cases degree"
+REAL_UNIT="--full --steps 0 --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 1 --real-cases unit"
 SQ1="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_F32 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE GRBM_COUNT"
 SQ2="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU SQ_INSTS_SALU SQ_VALU_MFMA_COEXEC_CYCLES"
 SQ3="SQ_INSTS_FLAT SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_WAVES"
@@ -76,6 +76,6 @@ if [ -n "${PART:-}" ]; then
 fi
 python scripts/rocprof_summary.py $OUT > /dev/null && cp $OUT/traffic.json profiles/traffic.json && echo "summary done"
 if [ "${2:-}" != "nobench" ]; then
-  timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   echo "bench rc=$?"
 fi

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/pmc_ab
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0 --steps 2 --warmup 1"
+ARGS="--full --batch-graphs 0 --c5-graphs 0 --no-cpu-baseline --degree-steps 0 --no-per-step --real-steps 0 --steps 2 --warmup 1"
 for cfg in ${CFGS:-base: loop:MD_EG_APPLY=0}; do
   name=${cfg%%:*}
   E=${cfg#*:}

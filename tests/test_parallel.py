@@ -89,7 +89,7 @@ def _bench(*extra):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--cpu-dry-run", "--n", "40", "--steps", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--cpu-dry-run", "--n", "40", "--steps", "1",
            "--warmup", "0", "--batch-steps", "1", "--degree-steps", "0", "--no-cpu-baseline", "--real-steps", "0"] + list(extra)
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
@@ -124,6 +124,40 @@ def test_bench_launcher_world2_gathers_like_one_process():
     assert c2["audc_all"] == c1["audc_all"] and c2["removals_all"] == c1["removals_all"]
     assert c2["removals_per_step"] == c1["removals_per_step"]
     assert two["dist_check"] == {"backend": "gloo", "world": 2, "gather_ok": True}
+
+
+@pytest.mark.timeout(300)
+def test_plain_bench_prints_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without `--full` the line holds the headline and nothing `--full` measures, with
+    `ms_per_step` of the `--steps` timed steps; `--dump-outputs DIR` writes what the last timed
+    step returned as float64 .npy files, the same from run to run (host stub engine)."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--cpu-dry-run", "--gpus", "1", "--n", "40",
+               "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)]
+        out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=240, env=env).stdout
+        lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out
+        line = json.loads(lines[0])
+        assert line["full"] is False and not set(bench.FULL_ONLY + ("cpu_baseline",)) & set(line)
+        assert line["metric"] == bench.METRIC and line["unit"] == "removals/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "fp32" and line["steps"] == 3 and line["warmup"] == 1
+        assert line["ms_per_step"] > 0
+        removals = line["config"]["removals_per_step"]
+        assert abs(line["value"] - removals / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+        assert sorted(os.listdir(tmp_path / d)) == ["max_rank.npy", "ranks.npy", "seq.npy"]
+        dumps.append({f: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+        assert all(a.dtype == np.float64 for a in dumps[-1].values())
+        assert len(dumps[-1]["seq.npy"]) == len(dumps[-1]["ranks.npy"]) == removals
+        assert dumps[-1]["max_rank.npy"].shape == (1,)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
 
 
 @pytest.mark.timeout(300)
