@@ -49,6 +49,17 @@ enum { MD_COST_UNIT = 0, MD_COST_DEGREE = 1 };
  *   w_layer2[128], trans[64][64], bias[64], logis.weight[64], logis.bias[1]          */
 #define MD_WEIGHT_FLOATS 31205
 
+/* Model: the unit/degree-cost network (two-column node input), or the community-enhanced one of
+ * CEMultiDismantler, whose node input has a third column, a static per-node, per-layer community
+ * prior (CEMultiDismantler/MultiDismantler_net_graphsage.py:255-285; the input rows are built in
+ * CEMultiDismantler/PrepareBatchGraph.py:140-148: a live node's row is [d/dmax, d/dmax, c], the
+ * virtual node's [1, 1, 0]).  Only the binary "boundary" prior (c in {0, 1}) is supported. */
+enum { MD_MODEL_BASE = 0, MD_MODEL_COMMUNITY = 1 };
+
+/* Packed weight blob of the community model: the order above with w_n2l[3][64] first (its third
+ * row multiplies the prior); every other tensor as in MD_WEIGHT_FLOATS (h2_weight[36]). */
+#define MD_WEIGHT_FLOATS_COMMUNITY 31269
+
 typedef struct md_ctx md_ctx;
 
 /* Host tie-resolution callback.  The device picks the arg-max itself whenever the
@@ -74,11 +85,30 @@ typedef int (*md_argsort_f64)(void* data, int64_t* idx, int64_t n, void* unused)
 /* Create a context on HIP device `device`.  `weights` holds MD_WEIGHT_FLOATS floats
  * (replaces MultiDismantler.LoadModel, U/MultiDismantler_torch.py:791-797). */
 md_status md_create(int device, const float* weights, size_t n_floats, int cost_mode, md_ctx** out);
+/* md_create with the model given: `weights` holds MD_WEIGHT_FLOATS (MD_MODEL_BASE) or
+ * MD_WEIGHT_FLOATS_COMMUNITY (MD_MODEL_COMMUNITY) floats, and n_floats must match the model
+ * (else MD_EINVAL).  md_create is md_create_model(..., MD_MODEL_BASE, ...).  The reference has no
+ * community model with degree cost: MD_MODEL_COMMUNITY with MD_COST_DEGREE is MD_EINVAL.
+ * A community context keeps the K2 end-game shortcut off (live nodes of a K2 state with
+ * different priors have different Q): one forward pass per removal step, as MD_VARIANT 2048. */
+md_status md_create_model(int device, const float* weights, size_t n_floats, int cost_mode, int model,
+                          md_ctx** out);
 void md_destroy(md_ctx* ctx);
 const char* md_last_error(const md_ctx* ctx);
 
-/* Replace the weights of an existing context (LoadModel on a live agent). */
+/* Replace the weights of an existing context (LoadModel on a live agent).  n_floats must be the
+ * blob size of the context's model. */
 md_status md_set_weights(md_ctx* ctx, const float* weights, size_t n_floats);
+
+/* Community model: the static prior column of the node input (the reference attaches it per graph
+ * as node_comm_feat, CEMultiDismantler/PrepareBatchGraph.py:140-148).  `prior` holds
+ * 2*sum(n_nodes) floats: layer 0 of all graphs, then layer 1, as node_w is laid out.  Valid after
+ * md_load_graphs, between launches; it touches no environment state and takes effect at the next
+ * prediction.  Every value must be exactly 0.0f or 1.0f (the "boundary" prior), else MD_EINVAL:
+ * participation-valued priors are not supported.  MD_ESTATE on a base-model context or before
+ * graphs are loaded.  md_load_graphs on a community context sets the prior to all zeros, the
+ * reference's own fallback when it has no partition. */
+md_status md_set_node_prior(md_ctx* ctx, const float* prior);
 
 /* Load a batch of two-layer graphs (replaces graph.Graph_test, U/graph.py:69-84, and
  * MultiDismantler.InsertGraph :171-178).  Graph g has n_nodes[g] nodes (ids 0..n-1).

@@ -17,12 +17,15 @@ LIB_PATH = os.environ.get("MD_LIB") or os.path.join(HERE, "libmdroll.so")
 MD_OK, MD_EINVAL, MD_EHIP, MD_EOOM, MD_ESTATE, MD_ETIMEOUT, MD_ECALLBACK = range(7)
 MD_COST_UNIT, MD_COST_DEGREE = 0, 1
 MD_WEIGHT_FLOATS = 31205
+MD_MODEL_BASE, MD_MODEL_COMMUNITY = 0, 1
+MD_WEIGHT_FLOATS_COMMUNITY = 31269  # w_n2l (3, 64): the community model's third input column
+MODEL_WEIGHT_FLOATS = {MD_MODEL_BASE: MD_WEIGHT_FLOATS, MD_MODEL_COMMUNITY: MD_WEIGHT_FLOATS_COMMUNITY}
 STATUS_NAMES = {1: "MD_EINVAL", 2: "MD_EHIP", 3: "MD_EOOM", 4: "MD_ESTATE", 5: "MD_ETIMEOUT", 6: "MD_ECALLBACK"}
 
 # Every symbol include/mdroll.h declares (checked by tests/test_abi.py).
 PROF_SLOTS = 96  # MD_PROF_SLOTS in include/mdroll.h
 
-EXPORTS = ("md_create", "md_destroy", "md_last_error", "md_set_weights", "md_load_graphs", "md_reset",
+EXPORTS = ("md_create", "md_create_model", "md_set_node_prior", "md_destroy", "md_last_error", "md_set_weights", "md_load_graphs", "md_reset",
            "md_reset_deferred", "md_max_rank",
            "md_predict", "md_step", "md_rollout", "md_rollout_packed", "md_rollout_trace", "md_get_state", "md_set_state",
            "md_set_team_size", "md_set_tie_argsort", "md_last_timing", "md_host_requests", "md_profile", "md_profile_read",
@@ -58,6 +61,9 @@ def load_library(path=LIB_PATH):
     vp = ctypes.c_void_p
     proto = {
         "md_create": (ctypes.c_int, [ctypes.c_int, _f32p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp)]),
+        "md_create_model": (ctypes.c_int, [ctypes.c_int, _f32p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(vp)]),
+        "md_set_node_prior": (ctypes.c_int, [vp, _f32p]),
         "md_destroy": (None, [vp]),
         "md_last_error": (ctypes.c_char_p, [vp]),
         "md_set_weights": (ctypes.c_int, [vp, _f32p, ctypes.c_size_t]),
@@ -129,14 +135,19 @@ def _argsort_select(q, n_out):
 class Engine:
     """One device context (md_ctx) holding weights and a batch of graphs."""
 
-    def __init__(self, weights, device=0, cost_mode=MD_COST_UNIT):
+    def __init__(self, weights, device=0, cost_mode=MD_COST_UNIT, model=None):
         self.lib = load_library()
         w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
-        if w.size != MD_WEIGHT_FLOATS:
-            raise ValueError(f"expected {MD_WEIGHT_FLOATS} packed weights, got {w.size}")
+        if model is None:  # inferred from the blob size
+            model = MD_MODEL_COMMUNITY if w.size == MD_WEIGHT_FLOATS_COMMUNITY else MD_MODEL_BASE
+        if model not in MODEL_WEIGHT_FLOATS:
+            raise ValueError(f"unknown model {model}")
+        if w.size != MODEL_WEIGHT_FLOATS[model]:
+            raise ValueError(f"expected {MODEL_WEIGHT_FLOATS[model]} packed weights, got {w.size}")
         self.cost_mode = cost_mode
+        self.model = model
         h = ctypes.c_void_p()
-        self._check(self.lib.md_create(device, _ptr(w, _f32p), w.size, cost_mode, ctypes.byref(h)), None)
+        self._check(self.lib.md_create_model(device, _ptr(w, _f32p), w.size, cost_mode, model, ctypes.byref(h)), None)
         self.h = h
         self.n_nodes = None
         self.node_off = None
@@ -192,6 +203,29 @@ class Engine:
         self.n_nodes = n
         self.node_off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
         self.n_edges = [np.diff(offs[l]) for l in range(2)]
+
+    def set_node_prior(self, priors):
+        """Community model: the static boundary prior of every loaded graph, a list of
+        (prior0, prior1) per graph, n_nodes values each, every value exactly 0 or 1
+        (md_set_node_prior; takes effect at the next prediction)."""
+        if self.model != MD_MODEL_COMMUNITY:
+            raise MDError("MD_ESTATE: node prior: not a community-model engine")
+        if self.n_nodes is None:
+            raise MDError("MD_ESTATE: node prior: no graphs loaded")
+        if len(priors) != len(self.n_nodes):
+            raise ValueError(f"expected priors of {len(self.n_nodes)} graphs, got {len(priors)}")
+        lay = [[], []]
+        for g, pr in enumerate(priors):
+            for l in range(2):
+                a = np.asarray(pr[l], dtype=np.float32).reshape(-1)
+                if a.size != int(self.n_nodes[g]):
+                    raise ValueError(f"graph {g}, layer {l}: expected {int(self.n_nodes[g])} prior values, got {a.size}")
+                if not np.all((a == 0.0) | (a == 1.0)):
+                    raise ValueError(f"graph {g}, layer {l}: the prior must be 0 or 1 per node "
+                                     "(participation-valued priors are not supported)")
+                lay[l].append(a)
+        flat = np.ascontiguousarray(np.concatenate(lay[0] + lay[1]), dtype=np.float32)
+        self._check(self.lib.md_set_node_prior(self.h, _ptr(flat, _f32p)))
 
     def reset(self):
         mr = np.zeros(len(self.n_nodes), np.int32)
@@ -323,7 +357,9 @@ class Engine:
 
 
 def pack_weights(arrays):
-    """Pack a reference state_dict (name -> array) into the MD_WEIGHT_FLOATS blob of mdroll.h."""
+    """Pack a reference state_dict (name -> array) into the weight blob of mdroll.h:
+    MD_WEIGHT_FLOATS floats for a (2, 64) w_n2l, MD_WEIGHT_FLOATS_COMMUNITY for the community
+    model's (3, 64) (same order, w_n2l's three rows first)."""
     order = ["w_n2l", "p_node_conv", "p_node_conv2", "p_node_conv3", "h1_weight", "h2_weight", "cross_product",
              "w_layer1", "w_layer2", "layerNodeAttention_weight.trans", "layerNodeAttention_weight.bias",
              "layerNodeAttention_weight.logis.parameter.weight", "layerNodeAttention_weight.logis.parameter.bias"]
@@ -334,5 +370,10 @@ def pack_weights(arrays):
             a = arrays["last_w"]
         parts.append(np.asarray(a, dtype=np.float32).reshape(-1))
     w = np.concatenate(parts)
-    assert w.size == MD_WEIGHT_FLOATS, w.size
+    rows = np.asarray(arrays["w_n2l"]).shape[0]
+    if rows not in (2, 3):
+        raise ValueError(f"w_n2l has {rows} rows: neither the base (2) nor the community (3) model")
+    want = MD_WEIGHT_FLOATS_COMMUNITY if rows == 3 else MD_WEIGHT_FLOATS
+    if w.size != want:
+        raise ValueError(f"state_dict packs to {w.size} floats, expected {want} (unsupported checkpoint layout)")
     return w

@@ -28,6 +28,7 @@ BATCH_SIZE = 64               # :54
 
 class MultiDismantler:
     cost_mode = _lib.MD_COST_UNIT
+    model = _lib.MD_MODEL_BASE  # agent_community: MD_MODEL_COMMUNITY
 
     def __init__(self, device=0):
         self.device = device
@@ -41,7 +42,7 @@ class MultiDismantler:
         self.model_file = None
         # the reference constructor's log lines (U/MultiDismantler_torch.py:107,124)
         print("CUDA:", _lib.device_count() > 0)
-        print("Total number of MultiDismantler_net parameters: {}".format(_lib.MD_WEIGHT_FLOATS))
+        print("Total number of MultiDismantler_net parameters: {}".format(_lib.MODEL_WEIGHT_FLOATS[self.model]))
 
     # ---------------------------------------------------------------- model / graphs
     @property
@@ -49,14 +50,14 @@ class MultiDismantler:
         if self._engine is None:
             if self._weights is None:
                 self.LoadModel(None)
-            self._engine = _lib.Engine(self._weights, device=self.device, cost_mode=self.cost_mode)
+            self._engine = _lib.Engine(self._weights, device=self.device, cost_mode=self.cost_mode, model=self.model)
             self.test_env.attach(self._engine)
         return self._engine
 
     def LoadModel(self, model_path):  # noqa: N802
         """Load a checkpoint (reference .ckpt via torch.load(weights_only=True), or .npz)."""
-        self.model_file = _engine.resolve_model(model_path, self.cost_mode)
-        self._weights = _engine.load_weights(self.model_file)
+        self.model_file = _engine.resolve_model(model_path, self.cost_mode, self.model)
+        self._weights = _engine.load_weights(self.model_file, model=self.model)
         if self._engine is not None:
             self._engine.set_weights(self._weights)
         print("restore model from file successfully")
@@ -94,6 +95,7 @@ class MultiDismantler:
             if not live_state:
                 env.graph = None
                 eng.load_graphs([(g.num_nodes, g.edges[0], g.edges[1])], node_w=self._node_w(g))
+                self._set_prior(eng, [g])
                 c = np.zeros(g.num_nodes, np.uint8)
                 c[list(cov)] = 1
                 rs = []
@@ -109,6 +111,9 @@ class MultiDismantler:
 
     def _node_w(self, g):
         return None
+
+    def _set_prior(self, eng, graphs):
+        """Hook of the community agent (the graphs' static prior, after load_graphs)."""
 
     # ---------------------------------------------------------------- rollouts
     def _device_rollout(self, g, step):
@@ -152,6 +157,7 @@ class MultiDismantler:
         eng = self.engine
         eng.load_graphs([(g.num_nodes, g.edges[0], g.edges[1]) for g in graphs],
                         node_w=self._batch_node_w(graphs))
+        self._set_prior(eng, graphs)
         mr = eng.reset()
         outs = eng.rollout(step=step)
         res = []
@@ -230,6 +236,12 @@ class MultiDismantler:
             flush()
         return None, layers
 
+    def _real_graph(self, test_name, num_nodes, layers, data_root):
+        """The two chosen layers of a multiplex file as a Graph_test (the community agent
+        attaches its prior here)."""
+        _, gl = self.read_multiplex(os.path.join(data_root, "real", test_name), num_nodes)
+        return _graph.Graph_test.from_edges(num_nodes, gl[layers[0] - 1], gl[layers[1] - 1])
+
     def EvaluateRealData(self, model_file, data_test, save_dir, stepRatio, num_nodes, layers, data_root="../../data"):  # noqa: N802,N803
         """testReal harness (:645-709): writes Soluion_*, NormalizedLMCC_* (unit cost)."""
         test_name = data_test.split("/")[-1]
@@ -239,8 +251,7 @@ class MultiDismantler:
         stem = test_name.split(".")[0]
         f1 = "%s/%s_%s_%s%s.%s" % (save_dir_local, "Soluion", stem, layers[0], layers[1], "txt")
         f2 = "%s/%s_%s_%s%s.%s" % (save_dir_local, "NormalizedLMCC", stem, layers[0], layers[1], "txt")
-        _, gl = self.read_multiplex(os.path.join(data_root, "real", test_name), num_nodes)
-        g = _graph.Graph_test.from_edges(num_nodes, gl[layers[0] - 1], gl[layers[1] - 1])
+        g = self._real_graph(test_name, num_nodes, layers, data_root)
         mcc_avg = [0] * g.num_nodes
         scores = []
         with open(f1, "w") as fo:

@@ -4,6 +4,8 @@
     python -m mdcommunity_amd.cli unit   testReal      --output DIR   # U/testReal.py
     python -m mdcommunity_amd.cli degree testSynthetic --output DIR   # D/testSynthetic.py
     python -m mdcommunity_amd.cli degree testReal      --output DIR   # D/testReal.py
+    python -m mdcommunity_amd.cli community testReal --output DIR --model CKPT   # CE/testReal.py
+    python -m mdcommunity_amd.cli community testSynthetic --output DIR --model CKPT
 
 Same inputs and outputs as the reference scripts: testSynthetic reads
 ``<data-root>/synthetic/<type>/syn_<N>/adj{1,2}_<i>.npy`` and writes
@@ -11,7 +13,9 @@ Same inputs and outputs as the reference scripts: testSynthetic reads
 ``<data-root>/real/<name>.edges`` and writes the harness files of EvaluateRealData plus
 ``StepRatio_<r>/time&audc_<name>.csv``.  Defaults are the reference scripts' own lists
 (U/testReal.py:24-66, D/testReal.py:24-60, U/testSynthetic.py:14-20); the rollouts run on the
-GPU through libmdroll.so.  Training (``train``, ``drawLmcc``) is out of scope.
+GPU through libmdroll.so.  The ``community`` variant is the community-enhanced model
+(CEMultiDismantler, boundary prior); no checkpoint of it is shipped, so ``--model`` is required
+unless the reference's default checkpoint path exists.  Training (``train``, ``drawLmcc``) is out of scope.
 """
 import argparse
 import os
@@ -22,6 +26,7 @@ import numpy as np
 UNIT_SYN_MODEL = "./models/g0.5_TORCH-Model_GMM_30_50/nrange_30_50_iter_100000.ckpt"   # U/testSynthetic.py:19
 UNIT_REAL_MODEL = "./models/g0-1_10w_TORCH-Model_GMM_30_50/nrange_30_50_iter_24000.ckpt"  # U/testReal.py:78-79
 DEGREE_MODEL = "./models/nrange_30_50_iter_100000.ckpt"                                   # D/testReal.py:79
+COMMUNITY_MODEL = "./models/g0-1_10w_TORCH-Model_GMM_30_50/nrange_30_50_iter_30000.ckpt"  # CE/testReal.py main()
 SYN_SIZES = ["32", "64", "128", "256", "512", "1024"]
 SYN_TYPES = ["data_g", "data_gamma", "data_k"]
 # (name, N, layers) as enabled in the reference scripts
@@ -29,11 +34,16 @@ UNIT_REAL = [("Padgett-Florentine-Families_multiplex", 16, (1, 2)),
              ("netsci_co-authorship_multiplex", 1400, (1, 2)),
              ("Lazega-Law-Firm_multiplex", 71, (1, 3))]
 DEGREE_REAL = [("fao_trade_multiplex", 214, (3, 24))]
+COMMUNITY_REAL = [("fao_trade_multiplex", 214, (3, 24)),            # CE/testReal.py:27-61
+                  ("celegans_connectome_multiplex", 279, (2, 3)),
+                  ("fb-tw", 1043, (1, 2))]
 
 
 def _agent(variant):
     if variant == "degree":
         from .agent_degree import MultiDismantler
+    elif variant == "community":
+        from .agent_community import MultiDismantler
     else:
         from .agent import MultiDismantler
     return MultiDismantler()
@@ -47,7 +57,7 @@ def _dataset(spec):
 
 def test_synthetic(variant, output, data_root, sizes, types, model=None):
     dqn = _agent(variant)
-    model_file = model or (DEGREE_MODEL if variant == "degree" else UNIT_SYN_MODEL)
+    model_file = model or {"degree": DEGREE_MODEL, "community": COMMUNITY_MODEL}.get(variant, UNIT_SYN_MODEL)
     lines = {}
     for data_type in types:
         file_path = output + data_type
@@ -66,7 +76,7 @@ def test_synthetic(variant, output, data_root, sizes, types, model=None):
 def test_real(variant, output, data_root, datasets, step_ratio=0.0, model=None):
     import pandas as pd
     dqn = _agent(variant)
-    model_file = model or (DEGREE_MODEL if variant == "degree" else UNIT_REAL_MODEL)
+    model_file = model or {"degree": DEGREE_MODEL, "community": COMMUNITY_MODEL}.get(variant, UNIT_REAL_MODEL)
     save_dir = output
     if not os.path.exists(save_dir):
         os.makedirs(save_dir, exist_ok=True)
@@ -94,7 +104,7 @@ def test_real(variant, output, data_root, datasets, step_ratio=0.0, model=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="mdcommunity_amd.cli", description=__doc__.split("\n\n")[0])
-    ap.add_argument("variant", choices=["unit", "degree"])
+    ap.add_argument("variant", choices=["unit", "degree", "community"])
     ap.add_argument("command", choices=["testSynthetic", "testReal", "train", "drawLmcc"])
     ap.add_argument("-o", "--output", required=True, help="path to output file")
     ap.add_argument("--data-root", default="../../data", help="directory holding synthetic/ and real/")
@@ -107,10 +117,12 @@ def main(argv=None):
     if a.command in ("train", "drawLmcc"):
         print("%s is not part of the MI355X inference engine (training and plotting are out of scope)" % a.command)
         return 2
+    if a.variant == "community" and a.model is None and not os.path.exists(COMMUNITY_MODEL):
+        ap.error("the community variant ships no checkpoint: --model is required (%s does not exist)" % COMMUNITY_MODEL)
     if a.command == "testSynthetic":
         test_synthetic(a.variant, a.output, a.data_root, a.sizes.split(","), a.types.split(","), a.model)
     else:
-        ds = [_dataset(s) for s in a.dataset] if a.dataset else (DEGREE_REAL if a.variant == "degree" else UNIT_REAL)
+        ds = [_dataset(s) for s in a.dataset] if a.dataset else {"degree": DEGREE_REAL, "community": COMMUNITY_REAL}.get(a.variant, UNIT_REAL)
         test_real(a.variant, a.output, a.data_root, ds, a.step_ratio, a.model)
     return 0
 

@@ -30,7 +30,7 @@ bool pfx_fits_host(int n, int edges);
 long long pfx_words_host(int edges);
 void build_weight_image(const float* w, float* img);
 hipError_t launch_rollout(const Params& p, const float* wimg, int grid, hipStream_t s);
-hipError_t launch_h0(const float* w, float* tab, int dm_lo, int dm_hi, hipStream_t s);
+hipError_t launch_h0(const float* w, float* tab, int dm_lo, int dm_hi, bool community, hipStream_t s);
 hipError_t launch_reset(const Params& p, hipStream_t s);
 hipError_t launch_clear(void* const* ptr, const size_t* bytes, int n, hipStream_t s);
 hipError_t set_kernel_attrs();
@@ -98,6 +98,7 @@ struct HostBuf {
 struct md_ctx {
   int device = 0;
   int cost_mode = MD_COST_UNIT;
+  int model = MD_MODEL_BASE;  // MD_MODEL_COMMUNITY: three-column node input, prior[] below
   int cus = 256;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -137,6 +138,7 @@ struct md_ctx {
   int team_owner = -1;      // the graph whose class labels gscr_team holds
   DevBuf<uint16_t> prank;   // static union ranks (team_env_step), graphs of <= 65535 nodes
   DevBuf<float> H[2][2], h0tab[2], q, spart, apart, ybuf, hbuf, tr_q, node_w;
+  DevBuf<uint8_t> prior;  // community model: [2][tot_n] boundary prior (0/1), layer 0 then layer 1
   DevBuf<unsigned long long> xbuf;
   DevBuf<int> nbc;  // neighbour-list cache slots (tiles of the largest launch)
   int nbc_slots = 0;
@@ -216,7 +218,7 @@ struct md_ctx {
     }
     covered.release(); live.release(); gscr.release(); pend.release(); tr_action.release(); tr_rank.release();
     tr_stat.release(); glist.release(); gtoff.release(); ctl.release(); tpart.release(); lab_ok.release(); gscr_team.release(); pfx.release(); bspec.release(); prank.release(); q.release(); spart.release();
-    apart.release(); ybuf.release(); hbuf.release(); xbuf.release(); nbc.release(); qslot.release(); qg.release(); tr_q.release(); node_w.release();
+    apart.release(); ybuf.release(); hbuf.release(); xbuf.release(); nbc.release(); qslot.release(); qg.release(); tr_q.release(); node_w.release(); prior.release();
     sres.release(); qspec.release(); bars.release(); dfbuf.release();
     df_graph.clear();
     h_req.release(); h_ans.release(); h_nact.release(); h_act.release(); h_q.release(); h_chk.release();
@@ -302,6 +304,8 @@ Params make_params(md_ctx* c) {
   p.tr_q = c->tr_q.p;
   p.node_w = c->cost_mode == MD_COST_DEGREE ? c->node_w.p : nullptr;
   p.h0g = c->h0g.p;
+  p.prior[0] = c->model == MD_MODEL_COMMUNITY ? c->prior.p : nullptr;
+  p.prior[1] = c->model == MD_MODEL_COMMUNITY ? c->prior.p + c->tot_n : nullptr;
   p.h0g_dm = c->h0g.p ? c->h0g_dm : 0;
   p.bar = (unsigned*)(c->ctl.p + CTL_BAR);
   p.bars = c->bars.p;
@@ -656,7 +660,7 @@ md_status launch_chunk(md_ctx* c, const int* gl_in, int ngl, int run_mode, int h
     // (the callback path keeps one request per step); MD_VARIANT bit 2048 turns it off
     // (bit 2: the answer applied in one pass, env_endgame_apply; MD_EG_APPLY=0: action by action)
     p.endgame = run_mode == RUN_ROLLOUT && c->tie_argsort != nullptr && sel->step == 1 &&
-                c->cost_mode == MD_COST_UNIT && !(c->variant & 2048)
+                c->cost_mode == MD_COST_UNIT && c->model == MD_MODEL_BASE && !(c->variant & 2048)
                     ? 1 | (c->eg_apply ? 2 : 0)
                     : 0;
   }
@@ -817,16 +821,27 @@ int md_device_count(void) {
 const char* md_last_error(const md_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 md_status md_create(int device, const float* weights, size_t n_floats, int cost_mode, md_ctx** out) {
+  return md_create_model(device, weights, n_floats, cost_mode, MD_MODEL_BASE, out);
+}
+
+static size_t model_weight_floats(int model) {
+  return model == MD_MODEL_COMMUNITY ? MD_WEIGHT_FLOATS_COMMUNITY : MD_WEIGHT_FLOATS;
+}
+
+md_status md_create_model(int device, const float* weights, size_t n_floats, int cost_mode, int model, md_ctx** out) {
   if (!out || !weights) return MD_EINVAL;
   *out = nullptr;
-  if (n_floats != MD_WEIGHT_FLOATS) return MD_EINVAL;
+  if (model != MD_MODEL_BASE && model != MD_MODEL_COMMUNITY) return MD_EINVAL;
+  if (n_floats != model_weight_floats(model)) return MD_EINVAL;
   if (cost_mode != MD_COST_UNIT && cost_mode != MD_COST_DEGREE) return MD_EINVAL;
+  if (model == MD_MODEL_COMMUNITY && cost_mode == MD_COST_DEGREE) return MD_EINVAL;  // no such variant
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MD_EHIP;
   if (device < 0 || device >= ndev) return MD_EINVAL;
   md_ctx* c = new md_ctx();
   c->device = device;
   c->cost_mode = cost_mode;
+  c->model = model;
   if (const char* v = std::getenv("MD_VARIANT")) c->variant = std::atoi(v);
   if (const char* v = std::getenv("MD_ENV_MODE")) c->env_mode = std::atoi(v);
   if (const char* v = std::getenv("MD_PAIR")) c->pair_on = std::atoi(v) != 0;
@@ -883,30 +898,45 @@ void md_destroy(md_ctx* ctx) {
 constexpr int H0G_MAX_DM = 2048;
 md_status ensure_h0g(md_ctx* c, int need, bool weights_changed) {
   if (c->cost_mode != MD_COST_UNIT || !c->h0g_on) return MD_OK;
-  need = std::min(need, H0G_MAX_DM);
+  // (the community model's tables hold two rows per degree: the same memory bound)
+  need = std::min(need, c->model == MD_MODEL_COMMUNITY ? H0G_MAX_DM * 7 / 10 : H0G_MAX_DM);
   if (weights_changed && c->h0g.p) c->h0g_dm = 0;
   if (need <= c->h0g_dm) return MD_OK;
-  const size_t rows = (size_t)h0g_row(need + 1, 1);
+  const bool community = c->model == MD_MODEL_COMMUNITY;  // two rows per (dmax, d)
+  const size_t rows = (size_t)h0g_row(need + 1, 1) * (community ? 2 : 1);
   if (!c->h0g.p || c->h0g.n < rows * EMB) {
     c->h0g.release();
     HIPCHK(c, c->h0g.alloc(rows * EMB));
     c->h0g_dm = 0;
   }
-  HIPCHK(c, launch_h0(c->w.p, c->h0g.p, c->h0g_dm + 1, need, c->stream));
+  HIPCHK(c, launch_h0(c->w.p, c->h0g.p, c->h0g_dm + 1, need, community, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->h0g_dm = need;
   return MD_OK;
 }
 
 md_status md_set_weights(md_ctx* c, const float* weights, size_t n_floats) {
-  if (!c || !weights || n_floats != MD_WEIGHT_FLOATS) return fail(c, MD_EINVAL, "weights: expected %d floats", MD_WEIGHT_FLOATS);
+  if (!c) return MD_EINVAL;
+  if (!weights || n_floats != model_weight_floats(c->model))
+    return fail(c, MD_EINVAL, "weights: expected %d floats", (int)model_weight_floats(c->model));
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->w.p) HIPCHK(c, c->w.alloc(W_TOTAL + 3));
+  // community blob: w_n2l[3][64] first.  The device keeps the base layout (rows 0-1, then the
+  // other tensors at their base offsets) with row 2 after it (W_N2L_C).
+  std::vector<float> base;
+  if (c->model == MD_MODEL_COMMUNITY) {
+    base.resize(W_TOTAL_C);
+    std::copy(weights, weights + 128, base.begin());
+    std::copy(weights + 192, weights + W_TOTAL_C, base.begin() + 128);
+    std::copy(weights + 128, weights + 192, base.begin() + W_N2L_C);
+    weights = base.data();
+  }
+  const size_t wn = c->model == MD_MODEL_COMMUNITY ? W_TOTAL_C : W_TOTAL;
+  if (!c->w.p) HIPCHK(c, c->w.alloc(wn + 3));
   const int ni = weight_image_floats();
   if (!c->wimg.p) HIPCHK(c, c->wimg.alloc(ni));
   std::vector<float> img(ni);
   build_weight_image(weights, img.data());
-  HIPCHK(c, hipMemcpyAsync(c->w.p, weights, sizeof(float) * W_TOTAL, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->w.p, weights, sizeof(float) * wn, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->wimg.p, img.data(), sizeof(float) * ni, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // degree cost: the static first-layer input depends on the weights
@@ -929,6 +959,24 @@ md_status md_set_weights(md_ctx* c, const float* weights, size_t n_floats) {
   } else if (c->h0g.p) {
     c->h0g_dm = 0;
   }
+  return MD_OK;
+}
+
+md_status md_set_node_prior(md_ctx* c, const float* prior) {
+  if (!c) return MD_EINVAL;
+  if (c->model != MD_MODEL_COMMUNITY) return fail(c, MD_ESTATE, "node prior: not a community-model context");
+  if (c->ng <= 0) return fail(c, MD_ESTATE, "node prior: no graphs loaded");
+  if (!prior) return fail(c, MD_EINVAL, "node prior: null array");
+  std::vector<uint8_t> b(2 * c->tot_n);
+  for (size_t i = 0; i < b.size(); ++i) {
+    if (prior[i] != 0.0f && prior[i] != 1.0f)
+      return fail(c, MD_EINVAL, "node prior: value %g at %zu is not 0 or 1 (participation-valued priors are not supported)",
+                  (double)prior[i], i);
+    b[i] = prior[i] != 0.0f;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->prior.p, b.data(), b.size(), hipMemcpyHostToDevice));
   return MD_OK;
 }
 
@@ -1079,7 +1127,7 @@ md_status md_load_graphs(md_ctx* c, int n_graphs, const int32_t* n_nodes, const 
     HIPCHK(c, c->ev[l].alloc(ev[l].size() + 4));
     HIPCHK(c, c->estate[l].alloc(te[l] + 16));  // + 16: whole-chunk reads of the last states
     HIPCHK(c, c->deg[l].alloc(tn));
-    HIPCHK(c, c->h0tab[l].alloc(tn * EMB));
+    HIPCHK(c, c->h0tab[l].alloc(tn * EMB * (c->model == MD_MODEL_COMMUNITY ? 2 : 1)));  // community: rows 2 d + c
     HIPCHK(c, c->H[l][0].alloc(tn * EMB));
     HIPCHK(c, c->H[l][1].alloc(tn * EMB));
     HIPCHK(c, hipMemcpyAsync(c->rowptr[l].p, rowptr[l].data(), sizeof(int) * rowptr[l].size(), hipMemcpyHostToDevice, c->stream));
@@ -1161,6 +1209,11 @@ md_status md_load_graphs(md_ctx* c, int n_graphs, const int32_t* n_nodes, const 
   if (c->h_done.h == nullptr) HIPCHK(c, c->h_done.alloc(2));
   HIPCHK(c, c->h_gvar.alloc((size_t)n_graphs * (sizeof(GraphVar) / sizeof(int))));
   HIPCHK(c, hipMemcpyAsync(c->ginfo.p, info.data(), sizeof(GraphInfo) * n_graphs, hipMemcpyHostToDevice, c->stream));
+  if (c->model == MD_MODEL_COMMUNITY) {
+    // the reference's fallback when no partition is available: an all-zero prior
+    HIPCHK(c, c->prior.alloc(2 * tn));
+    HIPCHK(c, hipMemsetAsync(c->prior.p, 0, 2 * tn, c->stream));
+  }
   if (c->cost_mode == MD_COST_DEGREE) {
     HIPCHK(c, c->node_w.alloc(2 * tn));
     HIPCHK(c, hipMemcpyAsync(c->node_w.p, node_w, sizeof(float) * 2 * tn, hipMemcpyHostToDevice, c->stream));

@@ -34,7 +34,10 @@ constexpr int Q_CAP = 1 << 18;   // queue-mode ring slots (items in flight << Q_
 enum WOff : int {
   W_N2L = 0, W_P1 = 128, W_P2 = 4224, W_P3 = 8320, W_H1 = 16512, W_W2 = 18560, W_CP = 18596,
   W_WL1 = 18660, W_WL2 = 26852, W_T = 26980, W_TB = 31076, W_LW = 31140, W_LB = 31204,
-  W_TOTAL = 31205
+  W_TOTAL = 31205,
+  // community model (MD_MODEL_COMMUNITY): w_n2l's third row (the prior's) is kept after the base
+  // layout on the device, so every other offset holds for both models
+  W_N2L_C = 31205, W_TOTAL_C = 31269
 };
 
 // Edge state (per undirected edge and layer).
@@ -214,6 +217,11 @@ struct Params {
   // actions as independent prefix fixed points, one per workgroup, when at least pfx_min remain
   int* pfx;                        // scratch, pfx_words(largest et) ints; null: off
   int pfx_min;                     // MD_PREFIX (0: off)
+  // community model (CEMultiDismantler/PrepareBatchGraph.py:140-148): static boundary prior c in
+  // {0, 1} per node and layer, null on base contexts.  A live node's input is [d/dmax, d/dmax, c],
+  // so the first-layer tables hold two rows per degree: row 2 d + c (h0g: 2 h0g_row(dm, d) + c;
+  // h0tab: 2 n rows per graph and layer)
+  const uint8_t* prior[2];
 };
 // global-mode environment scratch words per node (md_env.h env_view: parents, degrees) and the
 // grid-wide step's own words per node of the graph it runs (team_env_step, one graph per launch)

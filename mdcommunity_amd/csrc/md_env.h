@@ -1342,6 +1342,39 @@ __device__ __forceinline__ int env_apply_spec(const EnvView<false>& E, const int
   return lm;
 }
 
+// The community model's per-graph table of layer l for dmax dm: rows 2 d + c of the graph's 2 n
+// rows, c in {0, 1}, the 3-term chain [f, f, c] . w_n2l of md_h0c_kernel.  Not inlined: base
+// contexts never call it, and the environment step keeps its register allocation.
+__device__ __noinline__ void h0_update_community(KParams&, int node_off, int l, int dm) {
+  KParams& p = kp();
+  const float* wn = p.w + W_N2L;
+  const float* wc = p.w + W_N2L_C;
+  float* tab = p.h0tab[l] + (size_t)node_off * (2 * EMB);
+  for (int i = (int)threadIdx.x; i < 2 * dm; i += NTHREADS) {
+    const int d = 1 + (i >> 1);
+    const float f = (float)d / (float)dm, cf = (float)(i & 1);
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 64; ++c) {
+      const float x = fmaxf(fmaf(cf, wc[c], fmaf(f, wn[64 + c], fmaf(f, wn[c], 0.f))), 0.f);
+      acc[c & 7] = fmaf(x, x, acc[c & 7]);
+    }
+    const float den = fmaxf(sqrtf(sumsq8_finish(acc)), 1e-12f);
+#pragma unroll
+    for (int c4 = 0; c4 < 16; ++c4) {
+      float o[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = 4 * c4 + k;
+        o[k] = fmaxf(fmaf(cf, wc[c], fmaf(f, wn[64 + c], fmaf(f, wn[c], 0.f))), 0.f) / den;
+      }
+      stc4(tab, (2 * d + (i & 1)) * 256 + c4 * 16, make_float4(o[0], o[1], o[2], o[3]));
+    }
+  }
+}
+
 // ------------------------------------------------------------------ the environment step
 // Everything phase A does for one graph once the actions to apply are known: cover each
 // queued node and run the fixed point (s0 first if not done), then residual degrees, the
@@ -1354,14 +1387,23 @@ __device__ __forceinline__ int env_apply_spec(const EnvView<false>& E, const int
 // d = 1..dmax (the row recomputed for the norm pass and the store pass; w_n2l arrives as
 // scalar loads), the norm in torch's order (wave_norm64's).  The table depends on dmax
 // only, so it is rebuilt only when dmax changed (hd0, hd1: the dmax of the current tables).
+// CM: the caller may run on a community context (the environment step is compiled once without
+// the community fallback, so base contexts run the code they always ran, and once with it).
+template <bool CM>
 __device__ __forceinline__ void h0_update(KParams& p, const GraphInfo& gi, GraphVar& gv, int dm0, int dm1, int hd0, int hd1) {
   if (p.node_w == nullptr) {
     const float* wn = p.w + W_N2L;
     for (int l = 0; l < 2; ++l) {
       const int dm = l ? dm1 : dm0;
       if (dm == (l ? hd1 : hd0)) continue;
-      float* tab = p.h0tab[l] + (size_t)gi.node_off * EMB;  // degrees <= n-1 fit the graph's rows
       if (dm <= p.h0g_dm && p.h0g != nullptr) continue;  // the tiles read the precomputed table
+      if constexpr (CM) {
+        if (p.prior[0] != nullptr) {  // community model: two rows per degree (a call: its own registers)
+          h0_update_community(p, gi.node_off, l, dm);
+          continue;
+        }
+      }
+      float* tab = p.h0tab[l] + (size_t)gi.node_off * EMB;  // degrees <= n-1 fit the graph's rows
       if (dm <= p.h0g_dm) {
         // the table of this dmax is precomputed (md_h0_kernel at load): a 16-byte copy
         const float* src = p.h0g + h0g_row(dm, 1) * EMB;
@@ -1556,7 +1598,7 @@ __device__ __noinline__ int env_endgame_apply(KParams&, const GraphInfo gi, int 
   return m;
 }
 
-template <bool GL>
+template <bool GL, bool CM>
 __device__ __noinline__ int env_step(KParams&, const GraphInfo gi, GraphVar&, float*, int pend_n,
                         int pend_first, const float*, bool staged) {
   KParams& p = kp();  // kernel arguments through the implicit-argument SGPRs (uniform)
@@ -1833,7 +1875,7 @@ __device__ __noinline__ int env_step(KParams&, const GraphInfo gi, GraphVar&, fl
       if (p.prof != nullptr && ps < p.prof_cap) p.prof[(size_t)ps * PROF_SLOTS + 64] = wall_clock64();
     }
   }
-  h0_update(p, gi, gv, dm0, dm1, hd0, hd1);
+  h0_update<CM>(p, gi, gv, dm0, dm1, hd0, hd1);
   __syncthreads();
   MD_PROF_A(15);
   QENV(4);
@@ -2816,7 +2858,7 @@ __device__ bool team_env_step(KParams& p, Team& T, int g, int pend_n, int pend_f
       gv.twohop[0] = ag.th0;
       gv.twohop[1] = ag.th1;
     }
-    h0_update(p, gi, gv, ag.dm0, ag.dm1, hd0, hd1);
+    h0_update<true>(p, gi, gv, ag.dm0, ag.dm1, hd0, hd1);
     __syncthreads();
   }
   if (wdirty) *err |= TEAM_WDIRTY;

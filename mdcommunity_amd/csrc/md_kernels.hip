@@ -1021,8 +1021,12 @@ __device__ __forceinline__ bool phase_a(KParams&, int g, bool have_q, float* lds
     bool was_staged = staged && fits;
     staged = fits;
     if (eg_ans && fits && eg_apply(p, gi, pend_n, was_staged)) pend_first = PEND_APPLIED;
-    int err = fits ? env_step<false>(p, gi, gv, area, pend_n, pend_first, lds, was_staged)
-                   : env_step<true>(p, gi, gv, area, pend_n, pend_first, lds, false);
+    // (community contexts run the instantiation that holds the 2 n-row table fallback)
+    const bool cm = p.prior[0] != nullptr;
+    int err = fits ? (cm ? env_step<false, true>(p, gi, gv, area, pend_n, pend_first, lds, was_staged)
+                         : env_step<false, false>(p, gi, gv, area, pend_n, pend_first, lds, was_staged))
+                   : (cm ? env_step<true, true>(p, gi, gv, area, pend_n, pend_first, lds, false)
+                         : env_step<true, false>(p, gi, gv, area, pend_n, pend_first, lds, false));
     // the prebuild confirmation: the state after this phase A is exactly the speculative
     // result published early (one action, taken from it; an end-game below withdraws it)
     cw = ((unsigned long long)(unsigned)misc[57] << 32) | (unsigned)misc[56];
@@ -1050,8 +1054,9 @@ __device__ __forceinline__ bool phase_a(KParams&, int g, bool have_q, float* lds
         const int k = host_handshake(p, gi, g, gv.npred, 0.f, gv.n_live, misc, true);
         cw = 0ull;
         if (k > 0) {
-          err = fits ? env_step<false>(p, gi, gv, area, k, eg_apply(p, gi, k, staged) ? PEND_APPLIED : -1, lds, true)
-                     : env_step<true>(p, gi, gv, area, k, -1, lds, false);
+          // (the end-game answer: base contexts only)
+          err = fits ? env_step<false, false>(p, gi, gv, area, k, eg_apply(p, gi, k, staged) ? PEND_APPLIED : -1, lds, true)
+                     : env_step<true, false>(p, gi, gv, area, k, -1, lds, false);
           if (threadIdx.x == 0) {
             if (err) raise_err(p, err);
             gv.status = gv.alive[0] == 0 || gv.alive[1] == 0 ? ST_TERMINAL : ST_RUN;
@@ -1088,12 +1093,26 @@ __device__ __forceinline__ bool phase_a(KParams&, int g, bool have_q, float* lds
 // The precomputed table of the step's dmax (md_h0_kernel, at load) when it exists -- phase A
 // then copies nothing -- else the graph's own table, rebuilt by phase A.  The dmax load goes
 // out beside the degree loads it is needed with.
+// Community contexts (p.prior != null, a wave-uniform test) keep two rows per degree: a node of
+// residual degree d and boundary prior c reads row 2 d + c of the same bases, scaled by two.
+// Every gather site indexes through h0_row, so a single-graph launch and a batch launch read
+// the same rows.
+__device__ __forceinline__ const uint8_t* h0_prior(KParams& p, const GraphInfo& gi, int l) {
+  return p.prior[l] != nullptr ? p.prior[l] + gi.node_off : nullptr;
+}
+__device__ __forceinline__ int h0_row(const uint8_t* pr, int d, int v) { return pr != nullptr ? 2 * d + (int)pr[v] : d; }
+__device__ __forceinline__ int h0_cap(const uint8_t* pr, int n) { return pr != nullptr ? 2 * n : n; }
+// base of dmax dm's precomputed table: row d (2 d + c) at base + that many rows
+__device__ __forceinline__ const float* h0g_base(KParams& p, int dm) {
+  const long long r = h0g_row(dm, 1) - 1;
+  return p.h0g + (p.prior[0] != nullptr ? 2 * r : r) * EMB;
+}
 __device__ __forceinline__ const float* first_layer_rows(KParams& p, const GraphInfo& gi, int l) {
   if (p.h0g != nullptr) {
     const int dm = ldc(&p.gvar[gi.gidx].dmax[l]);
-    if (dm >= 1 && dm <= p.h0g_dm) return p.h0g + (h0g_row(dm, 1) - 1) * EMB;  // row d at base + d rows
+    if (dm >= 1 && dm <= p.h0g_dm) return h0g_base(p, dm);
   }
-  return p.h0tab[l] + (size_t)gi.node_off * EMB;
+  return p.h0tab[l] + (size_t)gi.node_off * (p.prior[0] != nullptr ? 2 * EMB : EMB);
 }
 
 __device__ __noinline__ void gather_tile(KParams&, const GraphInfo gi, int it, const int*, float*) {
@@ -1109,6 +1128,7 @@ __device__ __noinline__ void gather_tile(KParams&, const GraphInfo gi, int it, c
   const int* deg = p.deg[l] + gi.node_off;
   const float* hp;
   bool table = false;
+  const uint8_t* const pr = h0_prior(p, gi, l);
   if (it == 1) {
     table = p.node_w == nullptr;
     hp = table ? first_layer_rows(p, gi, l) : p.h0tab[l] + (size_t)gi.node_off * EMB;
@@ -1122,8 +1142,8 @@ __device__ __noinline__ void gather_tile(KParams&, const GraphInfo gi, int it, c
   if (v >= 0) {
     rb = rp[v];
     re = rp[v + 1];
-    const int ov = table ? ldc(deg + v) : v;
-    if (MD_BOK(v < gi.n && ov >= 0 && ov < gi.n, 1)) own = ldc4(hp, ov * 256 + qd * 16);
+    const int ov = table ? h0_row(pr, ldc(deg + v), v) : v;
+    if (MD_BOK(v < gi.n && ov >= 0 && ov < h0_cap(pr, gi.n), 1)) own = ldc4(hp, ov * 256 + qd * 16);
   }
   int nch = (re - rb + 15) >> 4;
   nch = max(nch, __shfl_xor(nch, 16, 64));
@@ -1132,7 +1152,7 @@ __device__ __noinline__ void gather_tile(KParams&, const GraphInfo gi, int it, c
     const int e = rb + 16 * ch + qd;
     int nb = -1;
     if (e < re && ldc(ca + e)) nb = adj[e];
-    if (table && nb >= 0) nb = ldc(deg + nb);
+    if (table && nb >= 0) nb = h0_row(pr, ldc(deg + nb), nb);
     const unsigned long long m = __ballot(nb >= 0);
     unsigned gm = (unsigned)(m >> (16 * grp)) & 0xFFFFu;
     // the alive neighbours in CSR order (== reference in_edges order), 4 rows x 4 loads in flight
@@ -1482,6 +1502,7 @@ __device__ __noinline__ void gather_tile2(KParams&, const GraphInfo gi, int it, 
   const int* deg = p.deg[l] + gi.node_off;
   const float* hp;
   bool table = false;
+  const uint8_t* const pr = h0_prior(p, gi, l);
   if (it == 1) {
     table = p.node_w == nullptr;
     hp = table ? first_layer_rows(p, gi, l) : p.h0tab[l] + (size_t)gi.node_off * EMB;
@@ -1494,8 +1515,8 @@ __device__ __noinline__ void gather_tile2(KParams&, const GraphInfo gi, int it, 
   const int v = rows[r];
   float4 own = {0.f, 0.f, 0.f, 0.f}, acc = {0.f, 0.f, 0.f, 0.f};
   if (v >= 0) {
-    const int ov = table ? ldc(deg + v) : v;
-    if (MD_BOK(v < gi.n && ov >= 0 && ov < gi.n, 1)) own = ldc4(hp, ov * 256 + qd * 16);
+    const int ov = table ? h0_row(pr, ldc(deg + v), v) : v;
+    if (MD_BOK(v < gi.n && ov >= 0 && ov < h0_cap(pr, gi.n), 1)) own = ldc4(hp, ov * 256 + qd * 16);
   }
   const int myoff = hdr[l * 16 + r], mycnt = hdr[32 + l * 16 + r];
   const int totl = hdr[128 + l];
@@ -1513,8 +1534,8 @@ __device__ __noinline__ void gather_tile2(KParams&, const GraphInfo gi, int it, 
       src[i] = -1;
       if (b < nbat && k < STG_ROWS * 16 && row < totl) {
         const int id = nbl[row];
-        src[i] = MD_BOK(id < gi.n, 4) ? (table ? ldc(deg + id) : id) : -1;
-        if (!MD_BOK(src[i] < gi.n, 5)) src[i] = -1;
+        src[i] = MD_BOK(id < gi.n, 4) ? (table ? h0_row(pr, ldc(deg + id), id) : id) : -1;
+        if (!MD_BOK(src[i] < h0_cap(pr, gi.n), 5)) src[i] = -1;
       }
     }
 #pragma unroll
@@ -1625,6 +1646,7 @@ __device__ __noinline__ void gather_tile2s(KParams&, const GraphInfo gi, int it,
   const int* deg = deg_ovr != nullptr ? deg_ovr : p.deg[l] + gi.node_off;
   const float* hp;
   bool table = false;
+  const uint8_t* const pr = h0_prior(p, gi, l);
   if (it == 1) {
     table = p.node_w == nullptr;
     hp = table ? (hp_ovr != nullptr ? hp_ovr : first_layer_rows(p, gi, l)) : p.h0tab[l] + (size_t)gi.node_off * EMB;
@@ -1639,14 +1661,16 @@ __device__ __noinline__ void gather_tile2s(KParams&, const GraphInfo gi, int it,
   // (a torn speculative slot, this step: the degree words of odd nodes read as 0)
   const bool torn = deg_ovr != nullptr && ((const int*)(lds_base() + L_MISC))[25] != 0;
   auto rdeg = [&](int x) { return torn && (x & 1) ? 0 : ldc(deg + x); };
-  auto row_of = [&](int d, int site) { return md_brec(d >= 1 && d <= dcap, site) ? d : -1; };
+  auto row_of = [&](int x, int site) {
+    const int d = rdeg(x);
+    return md_brec(d >= 1 && d <= dcap, site) ? h0_row(pr, d, x) : -1;
+  };
 #else
-  auto rdeg = [&](int x) { return ldc(deg + x); };
-  auto row_of = [&](int d, int) { return min(max(d, 1), dcap); };
+  auto row_of = [&](int x, int) { return h0_row(pr, min(max(ldc(deg + x), 1), dcap), x); };
 #endif
   if (v >= 0) {
-    const int ov = table ? row_of(rdeg(v), 22) : v;
-    if (ov >= 0 && MD_BOK(v < gi.n && ov < gi.n, 1)) own = ldc2(hp, ov * 256 + q * 8);
+    const int ov = table ? row_of(v, 22) : v;
+    if (ov >= 0 && MD_BOK(v < gi.n && ov < h0_cap(pr, gi.n), 1)) own = ldc2(hp, ov * 256 + q * 8);
   }
   const int myoff = hdr[l * 16 + r], mycnt = hdr[32 + l * 16 + r];
   const int totl = hdr[128 + l];
@@ -1662,8 +1686,8 @@ __device__ __noinline__ void gather_tile2s(KParams&, const GraphInfo gi, int it,
       src[i] = -1;
       if (b < nbat && k < SROWS * 16 && row < totl) {
         const int id = nbl[row];
-        src[i] = MD_BOK(id < gi.n, 4) ? (table ? row_of(rdeg(id), 23) : id) : -1;
-        if (!MD_BOK(src[i] < gi.n, 5)) src[i] = -1;
+        src[i] = MD_BOK(id < gi.n, 4) ? (table ? row_of(id, 23) : id) : -1;
+        if (!MD_BOK(src[i] < h0_cap(pr, gi.n), 5)) src[i] = -1;
       }
     }
 #pragma unroll
@@ -1951,7 +1975,7 @@ __device__ __forceinline__ bool spec_iteration1(KParams&, const GraphInfo gi, in
   if (p.node_w == nullptr) {  // unit cost: rows by degree, from the precomputed table of the result's dmax
     dm = ((const int*)(lds + L_MISC))[40];  // (read by prebuild_lists, which runs just before)
     if (p.h0g == nullptr || dm < 1 || dm > p.h0g_dm) return false;
-    hp = p.h0g + (h0g_row(dm, 1) - 1) * EMB;
+    hp = h0g_base(p, dm);
   }
   gather_tile2s(p, gi, 1, rows, scr, L, sl + sres_deg(et) + L * n, hp, dm);
   __syncthreads();
@@ -3321,6 +3345,7 @@ __device__ __noinline__ void gather_pair(KParams&, const GraphInfo gi, int it) {
   const int* deg = p.deg[l] + gi.node_off;
   const float* hp;
   bool table = false;
+  const uint8_t* const pr = h0_prior(p, gi, l);
   if (it == 1) {
     table = p.node_w == nullptr;
     hp = table ? first_layer_rows(p, gi, l) : p.h0tab[l] + (size_t)gi.node_off * EMB;
@@ -3339,8 +3364,8 @@ __device__ __noinline__ void gather_pair(KParams&, const GraphInfo gi, int it) {
     acc[rb] = make_float4(0.f, 0.f, 0.f, 0.f);
     const int v = rows[16 * rb + r];
     if (v >= 0) {
-      const int ov = table ? ldc(deg + v) : v;
-      if (MD_BOK(v < gi.n && ov >= 0 && ov < gi.n, 1)) own[rb] = ldc4(hp, ov * 256 + qd * 16);
+      const int ov = table ? h0_row(pr, ldc(deg + v), v) : v;
+      if (MD_BOK(v < gi.n && ov >= 0 && ov < h0_cap(pr, gi.n), 1)) own[rb] = ldc4(hp, ov * 256 + qd * 16);
     }
   }
   const int t0 = h0[128 + l], totl = t0 + h1[128 + l];
@@ -3357,8 +3382,8 @@ __device__ __noinline__ void gather_pair(KParams&, const GraphInfo gi, int it) {
       src[i] = -1;
       if (b < nbat && k < STG2_ROWS * 16 && row < totl) {
         const int id = row < t0 ? nb0[row] : nb1[row - t0];
-        src[i] = MD_BOK(id < gi.n, 4) ? (table ? ldc(deg + id) : id) : -1;
-        if (!MD_BOK(src[i] < gi.n, 5)) src[i] = -1;
+        src[i] = MD_BOK(id < gi.n, 4) ? (table ? h0_row(pr, ldc(deg + id), id) : id) : -1;
+        if (!MD_BOK(src[i] < h0_cap(pr, gi.n), 5)) src[i] = -1;
       }
     }
 #pragma unroll
@@ -3483,6 +3508,7 @@ __device__ __noinline__ void gather_pair_csr(KParams&, const GraphInfo gi, int i
   const int* deg = p.deg[l] + gi.node_off;
   const float* hp;
   bool table = false;
+  const uint8_t* const pr = h0_prior(p, gi, l);
   if (it == 1) {
     table = p.node_w == nullptr;
     hp = table ? first_layer_rows(p, gi, l) : p.h0tab[l] + (size_t)gi.node_off * EMB;
@@ -3497,8 +3523,8 @@ __device__ __noinline__ void gather_pair_csr(KParams&, const GraphInfo gi, int i
     if (v >= 0) {
       rbeg = rp[v];
       rend = rp[v + 1];
-      const int ov = table ? ldc(deg + v) : v;
-      if (MD_BOK(v < gi.n && ov >= 0 && ov < gi.n, 1)) own = ldc4(hp, ov * 256 + qd * 16);
+      const int ov = table ? h0_row(pr, ldc(deg + v), v) : v;
+      if (MD_BOK(v < gi.n && ov >= 0 && ov < h0_cap(pr, gi.n), 1)) own = ldc4(hp, ov * 256 + qd * 16);
     }
     int nch = (rend - rbeg + 15) >> 4;
     nch = max(nch, __shfl_xor(nch, 16, 64));
@@ -3507,7 +3533,7 @@ __device__ __noinline__ void gather_pair_csr(KParams&, const GraphInfo gi, int i
       const int e = rbeg + 16 * ch + qd;
       int nb = -1;
       if (e < rend && ldc(ca + e)) nb = adj[e];
-      if (table && nb >= 0) nb = ldc(deg + nb);
+      if (table && nb >= 0) nb = h0_row(pr, ldc(deg + nb), nb);
       const unsigned long long m = __ballot(nb >= 0);
       unsigned gm = (unsigned)(m >> (16 * grp)) & 0xFFFFu;
       while (__any(gm != 0)) {
@@ -5564,6 +5590,32 @@ __global__ void __launch_bounds__(256) md_h0_kernel(const float* __restrict__ w,
   }
 }
 
+// The community model's tables: two rows per (dmax, d), row 2 h0g_row(dm, d) + c for the prior
+// c in {0, 1}: normalize(relu([f, f, c] . w_n2l)) with the 3-term FMA chain (w_n2l's third row at
+// W_N2L_C), the norm in the same order (CEMultiDismantler/MultiDismantler_net_graphsage.py:255-285).
+__global__ void __launch_bounds__(256) md_h0c_kernel(const float* __restrict__ w, float* tab, int dm_lo, int dm_hi) {
+  const int dm = dm_lo + (int)blockIdx.x;
+  if (dm > dm_hi) return;
+  const float* wn = w + W_N2L;
+  const float* wc = w + W_N2L_C;
+  for (int i = (int)threadIdx.x; i < 2 * dm; i += blockDim.x) {
+    const int d = 1 + (i >> 1);
+    const float f = (float)d / (float)dm, cf = (float)(i & 1);
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 64; ++c) {
+      const float x = fmaxf(fmaf(cf, wc[c], fmaf(f, wn[64 + c], fmaf(f, wn[c], 0.f))), 0.f);
+      acc[c & 7] = fmaf(x, x, acc[c & 7]);
+    }
+    const float den = fmaxf(sqrtf(sumsq8_finish(acc)), 1e-12f);
+    float* row = tab + (2 * h0g_row(dm, d) + (i & 1)) * EMB;
+#pragma unroll
+    for (int c = 0; c < 64; ++c) row[c] = fmaxf(fmaf(cf, wc[c], fmaf(f, wn[64 + c], fmaf(f, wn[c], 0.f))), 0.f) / den;
+  }
+}
+
 __global__ void md_reset_kernel(Params p) {
   const int gidx = blockIdx.x;
   if (gidx >= p.nglist) return;
@@ -5646,9 +5698,12 @@ hipError_t launch_rollout(const Params& p, const float* wimg, int grid, hipStrea
   return hipGetLastError();
 }
 
-hipError_t launch_h0(const float* w, float* tab, int dm_lo, int dm_hi, hipStream_t s) {
+hipError_t launch_h0(const float* w, float* tab, int dm_lo, int dm_hi, bool community, hipStream_t s) {
   if (dm_hi < dm_lo) return hipSuccess;
-  hipLaunchKernelGGL(md_h0_kernel, dim3(dm_hi - dm_lo + 1), dim3(256), 0, s, w, tab, dm_lo, dm_hi);
+  if (community)
+    hipLaunchKernelGGL(md_h0c_kernel, dim3(dm_hi - dm_lo + 1), dim3(256), 0, s, w, tab, dm_lo, dm_hi);
+  else
+    hipLaunchKernelGGL(md_h0_kernel, dim3(dm_hi - dm_lo + 1), dim3(256), 0, s, w, tab, dm_lo, dm_hi);
   return hipGetLastError();
 }
 

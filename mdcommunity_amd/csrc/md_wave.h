@@ -314,6 +314,7 @@ __device__ __forceinline__ void wq_gather_csr(KParams& p, const GraphInfo& gi, c
   const int* adj = p.adj[l] + gi.coff[l];
   const uint8_t* ca = p.calive[l] + gi.coff[l];
   const int* deg = p.deg[l] + gi.node_off;
+  const uint8_t* const pr = h0_prior(p, gi, l);
   for (int r = 0; r < TILE; ++r) {
     const int v = __shfl(vrow, r, 64);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -323,7 +324,7 @@ __device__ __forceinline__ void wq_gather_csr(KParams& p, const GraphInfo& gi, c
         const int e = c0 + lane;
         int nb = -1;
         if (e < re && ldc(ca + e)) nb = adj[e];
-        if (table && nb >= 0) nb = ldc(deg + nb);
+        if (table && nb >= 0) nb = h0_row(pr, ldc(deg + nb), nb);
         unsigned long long m = __ballot(nb >= 0);
         while (m != 0ull) {
           int src[4];
@@ -735,7 +736,8 @@ __device__ __forceinline__ void wq_tile(KParams&, int g, int gl, int it, int j) 
   const int nv = __popcll(__ballot(lane < TILE && vrow >= 0));
   built = wq_uni(built);
   const int tot0 = __shfl(hdx, 0, 64), tot1 = __shfl(hdx, 1, 64), okf = __shfl(hdx, 2, 64);
-  const bool ok = cacheable && built != 0 && okf != 0;
+  // (community contexts: a list entry becomes the row 2 d + c, which must fit its 16 bits)
+  const bool ok = cacheable && built != 0 && okf != 0 && (p.prior[0] == nullptr || gi.n <= 32768);
   const bool listed0 = ok && tot0 <= WQ_LIST_MAX, listed1 = ok && tot1 <= WQ_LIST_MAX;
   // both layers' list entries (packed two per int) into WL
   {
@@ -761,9 +763,11 @@ __device__ __forceinline__ void wq_tile(KParams&, int g, int gl, int it, int j) 
   const float* hp0 = wq_src(p, gi, it, 0, table);
   const float* hp1 = wq_src(p, gi, it, 1, table);
   int vs0 = vrow, vs1 = vrow;
+  const uint8_t* const pr0 = h0_prior(p, gi, 0);
+  const uint8_t* const pr1 = h0_prior(p, gi, 1);
   if (table && lane < TILE && vrow >= 0) {
-    vs0 = ldc(p.deg[0] + gi.node_off + vrow);
-    vs1 = ldc(p.deg[1] + gi.node_off + vrow);
+    vs0 = h0_row(pr0, ldc(p.deg[0] + gi.node_off + vrow), vrow);
+    vs1 = h0_row(pr1, ldc(p.deg[1] + gi.node_off + vrow), vrow);
   }
   float xa0[16], xa1[16];
   wq_xload(hp0, __shfl(vs0, lane & 15, 64), xa0);
@@ -777,8 +781,8 @@ __device__ __forceinline__ void wq_tile(KParams&, int g, int gl, int it, int j) 
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int i = i0 + lane + 64 * u;
-        d0[u] = i < t0 ? ldc(dg0 + (int)wl[i]) : 0;
-        d1[u] = i < t1 ? ldc(dg1 + (int)w1[i]) : 0;
+        d0[u] = i < t0 ? h0_row(pr0, ldc(dg0 + (int)wl[i]), (int)wl[i]) : 0;
+        d1[u] = i < t1 ? h0_row(pr1, ldc(dg1 + (int)w1[i]), (int)w1[i]) : 0;
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {

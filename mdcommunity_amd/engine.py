@@ -25,7 +25,27 @@ DEFAULT_DEGREE = os.path.join(WEIGHTS_DIR, "degree_iter100000.npz")
 SHIPPED_COST = {npz: cost for npz, cost in KNOWN_CKPTS.values()}
 
 
-def resolve_model(path, cost_mode=None):
+def check_model_rows(rows, model, path):
+    """Refuse a checkpoint of the other model: w_n2l has 2 rows in the base (unit / degree cost)
+    network and 3 in the community-enhanced one (CEMultiDismantler)."""
+    if model is None:
+        return
+    if model == _lib.MD_MODEL_BASE and rows == 3:
+        raise ValueError(f"{path} is a community-enhanced checkpoint (w_n2l has 3 rows); this agent runs the base "
+                         "model: use mdcommunity_amd.agent_community (cli variant 'community')")
+    if model == _lib.MD_MODEL_COMMUNITY and rows == 2:
+        raise ValueError(f"{path} is a base-model checkpoint (w_n2l has 2 rows); the community agent needs a "
+                         "CEMultiDismantler checkpoint (w_n2l with 3 rows)")
+    if rows not in (2, 3):
+        raise ValueError(f"{path}: w_n2l has {rows} rows (expected 2 or 3)")
+
+
+def _npz_w_n2l_rows(path):
+    with np.load(path, allow_pickle=False) as z:
+        return int(z["w_n2l"].shape[0]) if "w_n2l" in z.files else None
+
+
+def resolve_model(path, cost_mode=None, model=None):
     """Map a reference checkpoint path to a loadable file.
 
     An existing file is returned as is.  Otherwise the path must name one of the reference's
@@ -33,8 +53,13 @@ def resolve_model(path, cost_mode=None):
     optionally under its variant directory); the shipped .npz converted from it is returned.
     With ``cost_mode`` given, a shipped checkpoint of the other cost model is refused (the
     unit-cost agent must not silently run degree-cost weights, or the reverse).  Anything
-    else raises FileNotFoundError.
+    else raises FileNotFoundError.  With ``model`` given (_lib.MD_MODEL_*), a file of the other
+    model (by the rows of its w_n2l) is refused: .npz files here, .ckpt files when load_state
+    has read them.
     """
+    if model == _lib.MD_MODEL_COMMUNITY and (path is None or not os.path.exists(path)):
+        raise FileNotFoundError(f"{path}: no community-enhanced checkpoint is shipped; name an existing "
+                                "CEMultiDismantler .ckpt or a converted .npz")
     if path is None:
         return DEFAULT_DEGREE if cost_mode == _lib.MD_COST_DEGREE else DEFAULT_UNIT
     if os.path.exists(path):
@@ -43,6 +68,10 @@ def resolve_model(path, cost_mode=None):
                 and os.path.dirname(os.path.abspath(path)) == WEIGHTS_DIR):
             raise ValueError(f"{path} holds {'degree' if shipped else 'unit'}-cost weights; this agent is "
                              f"{'degree' if cost_mode else 'unit'} cost")
+        if model is not None and path.endswith(".npz"):
+            rows = _npz_w_n2l_rows(path)
+            if rows is not None:
+                check_model_rows(rows, model, path)
         return path
     norm = os.path.normpath(path.replace("\\", "/")).replace("\\", "/")
     parts = norm.split("/")
@@ -60,20 +89,24 @@ def resolve_model(path, cost_mode=None):
                             f"({', '.join(k for _, k in KNOWN_CKPTS)})")
 
 
-def load_state(path, cost_mode=None):
+def load_state(path, cost_mode=None, model=None):
     """state_dict arrays of a model file: .npz (ours) or a reference .ckpt loaded with
     torch.load(weights_only=True) (U/MultiDismantler_torch.py:791-797)."""
-    path = resolve_model(path, cost_mode)
+    path = resolve_model(path, cost_mode, model)
     if path.endswith(".npz"):
         with np.load(path, allow_pickle=False) as z:
-            return {k: z[k] for k in z.files}
-    import torch
-    sd = torch.load(path, weights_only=True, map_location="cpu")
-    return {k: v.detach().cpu().numpy() for k, v in sd.items()}
+            sd = {k: z[k] for k in z.files}
+    else:
+        import torch
+        sd = torch.load(path, weights_only=True, map_location="cpu")
+        sd = {k: v.detach().cpu().numpy() for k, v in sd.items()}
+    if model is not None and "w_n2l" in sd:
+        check_model_rows(int(np.asarray(sd["w_n2l"]).shape[0]), model, path)
+    return sd
 
 
-def load_weights(path, cost_mode=None):
-    return _lib.pack_weights(load_state(path, cost_mode))
+def load_weights(path, cost_mode=None, model=None):
+    return _lib.pack_weights(load_state(path, cost_mode, model))
 
 
 _mcc_engine = None

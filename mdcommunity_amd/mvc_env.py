@@ -42,6 +42,10 @@ class MvcEnv:
             from .graph import node_weight_array
             nw = node_weight_array([g])
         self.engine.load_graphs([(g.num_nodes, g.edges[0], g.edges[1])], node_w=nw)
+        if getattr(self.engine, "model", _lib.MD_MODEL_BASE) == _lib.MD_MODEL_COMMUNITY:
+            # the graph's static community prior (CE/PrepareBatchGraph.py:140-148); none: zeros
+            from .community import graph_prior
+            self.engine.set_node_prior([graph_prior(g)])
 
     # -- reference API
     def s0(self, g):
