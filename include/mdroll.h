@@ -168,6 +168,38 @@ md_status md_rollout(md_ctx* ctx, int step, int32_t* seq_out, int32_t* lmcc_out,
 md_status md_rollout_packed(md_ctx* ctx, int step, int32_t* seq_packed, int32_t* lmcc_packed, int32_t* seq_len,
                             md_select_cb cb, void* user);
 
+/* The reference's hand-written baselines as device rollouts (baseline/HDA/hda_2max.py, hda_add.py,
+ * baseline/CI/ci_max.py, ci_add.py: every removal there reruns MCC(G1, G2), the environment's own
+ * mutual-LMCC cascade).  The pick is the live node (layer-0 residual degree > 0) of largest
+ * integer score, the smallest id among equals (the max scripts' stable sorted(..., reverse=True)
+ * over nodes in id order; the add scripts draw among the maxima with random.choice and ci_add
+ * removes nodes past LMCC 1: here ADD takes the same deterministic rule and the same stop):
+ *   MD_HEUR_HDA  s_l(v) = d_l(v), the residual degree in layer l
+ *   MD_HEUR_CI   s_l(v) = -1 if d_l(v) == 0, else (d_l(v) - 1) * sum_{u in N_l(v)} (d_l(u) - 1)
+ *   MD_COMBINE_MAX  max(s_0, s_1);  MD_COMBINE_ADD  s_0 + s_1
+ * Scores are compared as 64-bit integers, so no input size is rejected: the LDS-resident kernel
+ * sums a node's neighbour term in 32 bits, which holds for every graph it takes (n <= 65535:
+ * at most 65534 * 65535 < 2^32), and the pick kernel over the HBM state sums in 64 bits.
+ * The rollout runs from the current state to terminal (the scripts' ND_temp == 1); a graph
+ * already terminal takes no removal.  Valid after md_reset, after md_reset_deferred (the s0 prune
+ * runs first, inside the launch) and on a partly dismantled state.  Outputs as md_rollout: the
+ * removals since the last reset (those of earlier md_step calls first), their LMCC sizes, their
+ * count.  The weights and a community context's prior are not read.  md_get_state, md_step,
+ * md_predict, md_last_timing and md_max_rank see the state it leaves.
+ * MD_ESTATE: no graphs loaded; MD_EINVAL: unknown kind or combine, or a degree-cost context (the
+ * MultiDismantler_degree_cost baselines score differently).
+ * A graph whose environment fits one workgroup's LDS runs its whole rollout resident there
+ * (one launch for all such graphs); a larger one, and every graph under MD_VARIANT 64, takes one
+ * pick launch and one environment-step launch per removal. */
+enum { MD_HEUR_HDA = 0, MD_HEUR_CI = 1 };
+enum { MD_COMBINE_MAX = 0, MD_COMBINE_ADD = 1 };
+md_status md_heuristic_rollout(md_ctx* ctx, int kind, int combine, int32_t* seq_out, int32_t* lmcc_out,
+                               int32_t* seq_len);
+
+/* 1 when md_heuristic_rollout runs a graph of n_nodes nodes and n_edges undirected edges (both
+ * layers together) resident in LDS, 0 when it takes the HBM path (MD_VARIANT 64 aside). */
+int md_heuristic_fits_lds(int n_nodes, int n_edges);
+
 /* Per-step diagnostics of the last md_rollout for graph g (capacity n_nodes[g] rows):
  * live nodes, alive edges in layer 0 and 1, number of nodes tied at the max, per prediction,
  * and (float) the best Q and top-2 gap.  Returns the number of predictions made. */

@@ -20,6 +20,10 @@ MD_WEIGHT_FLOATS = 31205
 MD_MODEL_BASE, MD_MODEL_COMMUNITY = 0, 1
 MD_WEIGHT_FLOATS_COMMUNITY = 31269  # w_n2l (3, 64): the community model's third input column
 MODEL_WEIGHT_FLOATS = {MD_MODEL_BASE: MD_WEIGHT_FLOATS, MD_MODEL_COMMUNITY: MD_WEIGHT_FLOATS_COMMUNITY}
+MD_HEUR_HDA, MD_HEUR_CI = 0, 1
+MD_COMBINE_MAX, MD_COMBINE_ADD = 0, 1
+HEUR_KINDS = {"hda": MD_HEUR_HDA, "ci": MD_HEUR_CI}
+HEUR_COMBINES = {"max": MD_COMBINE_MAX, "add": MD_COMBINE_ADD}
 STATUS_NAMES = {1: "MD_EINVAL", 2: "MD_EHIP", 3: "MD_EOOM", 4: "MD_ESTATE", 5: "MD_ETIMEOUT", 6: "MD_ECALLBACK"}
 
 # Every symbol include/mdroll.h declares (checked by tests/test_abi.py).
@@ -27,7 +31,7 @@ PROF_SLOTS = 96  # MD_PROF_SLOTS in include/mdroll.h
 
 EXPORTS = ("md_create", "md_create_model", "md_set_node_prior", "md_destroy", "md_last_error", "md_set_weights", "md_load_graphs", "md_reset",
            "md_reset_deferred", "md_max_rank",
-           "md_predict", "md_step", "md_rollout", "md_rollout_packed", "md_rollout_trace", "md_get_state", "md_set_state",
+           "md_predict", "md_step", "md_rollout", "md_rollout_packed", "md_heuristic_rollout", "md_heuristic_fits_lds", "md_rollout_trace", "md_get_state", "md_set_state",
            "md_set_team_size", "md_set_tie_argsort", "md_last_timing", "md_host_requests", "md_profile", "md_profile_read",
            "md_version", "md_device_count", "md_spec_stats", "md_gmm_last_error", "md_gmm_nodes", "md_gmm_links")
 
@@ -75,6 +79,8 @@ def load_library(path=LIB_PATH):
         "md_step": (ctypes.c_int, [vp, _i32p, _i32p, _u8p]),
         "md_rollout": (ctypes.c_int, [vp, ctypes.c_int, _i32p, _i32p, _i32p, SELECT_CB_ADDR, vp]),
         "md_rollout_packed": (ctypes.c_int, [vp, ctypes.c_int, _i32p, _i32p, _i32p, SELECT_CB_ADDR, vp]),
+        "md_heuristic_rollout": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p]),
+        "md_heuristic_fits_lds": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
         "md_rollout_trace": (ctypes.c_int, [vp, ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p, _i32p]),
         "md_spec_stats": (ctypes.c_int, [vp, ctypes.c_int, _i32p, _i32p]),
         "md_get_state": (ctypes.c_int, [vp, ctypes.c_int, _u8p, _u8p, _u8p, _i32p]),
@@ -105,6 +111,11 @@ def load_library(path=LIB_PATH):
 def device_count():
     """Visible GPUs (md_device_count; 0 without a GPU or when the runtime fails)."""
     return int(load_library().md_device_count())
+
+
+def heuristic_fits_lds(n_nodes, n_edges):
+    """Whether heuristic_rollout keeps a graph of this size resident in LDS (else the HBM path)."""
+    return bool(load_library().md_heuristic_fits_lds(int(n_nodes), int(n_edges)))
 
 
 def _ptr(a, t):
@@ -299,6 +310,25 @@ class Engine:
         ends = np.cumsum(ln).tolist()
         starts = [0] + ends[:-1]
         return [(seq[a:b], lm[a:b]) for a, b in zip(starts, ends)]
+
+    def heuristic_rollout(self, kind="hda", combine="max"):
+        """The reference's HDA / CI baseline as a device rollout from the current state to terminal
+        (md_heuristic_rollout): kind "hda" | "ci" (or MD_HEUR_*), combine "max" | "add" (or
+        MD_COMBINE_*).  Returns [(removals, LMCC sizes)] per graph, as rollout()."""
+        k = HEUR_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+        cb = HEUR_COMBINES.get(combine, combine) if isinstance(combine, str) else int(combine)
+        if isinstance(k, str) or isinstance(cb, str):
+            raise ValueError(f"unknown heuristic {kind!r} / combine {combine!r}")
+        if self.n_nodes is None:
+            raise MDError("MD_ESTATE: no graphs loaded")
+        tot = int(self.node_off[-1])
+        seq = np.empty(tot, np.int32)
+        lm = np.empty(tot, np.int32)
+        ln = np.zeros(len(self.n_nodes), np.int32)
+        self._check(self.lib.md_heuristic_rollout(self.h, k, cb, _ptr(seq, _i32p), _ptr(lm, _i32p), _ptr(ln, _i32p)))
+        off = self.node_off
+        return [(seq[int(off[g]):int(off[g]) + int(ln[g])].copy(), lm[int(off[g]):int(off[g]) + int(ln[g])].copy())
+                for g in range(len(ln))]
 
     def trace(self, g):
         n = int(self.n_nodes[g])

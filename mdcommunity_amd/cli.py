@@ -6,6 +6,8 @@
     python -m mdcommunity_amd.cli degree testReal      --output DIR   # D/testReal.py
     python -m mdcommunity_amd.cli community testReal --output DIR --model CKPT   # CE/testReal.py
     python -m mdcommunity_amd.cli community testSynthetic --output DIR --model CKPT
+    python -m mdcommunity_amd.cli baseline testReal --method {hda,ci} --combine {max,add} -o DIR \
+        --dataset name:N:l1,l2                                        # baseline/HDA, baseline/CI scripts
 
 Same inputs and outputs as the reference scripts: testSynthetic reads
 ``<data-root>/synthetic/<type>/syn_<N>/adj{1,2}_<i>.npy`` and writes
@@ -15,7 +17,10 @@ Same inputs and outputs as the reference scripts: testSynthetic reads
 (U/testReal.py:24-66, D/testReal.py:24-60, U/testSynthetic.py:14-20); the rollouts run on the
 GPU through libmdroll.so.  The ``community`` variant is the community-enhanced model
 (CEMultiDismantler, boundary prior); no checkpoint of it is shipped, so ``--model`` is required
-unless the reference's default checkpoint path exists.  Training (``train``, ``drawLmcc``) is out of scope.
+unless the reference's default checkpoint path exists.  The ``baseline`` variant runs the
+reference's HDA / CI heuristics (mdcommunity_amd.baselines) on the datasets given with
+``--dataset`` and writes the scripts' ``remove_nodes*`` / ``MaxCCList_Strategy_*`` files into the
+output directory; it loads no model.  Training (``train``, ``drawLmcc``) is out of scope.
 """
 import argparse
 import os
@@ -102,9 +107,18 @@ def test_real(variant, output, data_root, datasets, step_ratio=0.0, model=None):
     return out
 
 
+def test_baseline(output, data_root, datasets, method, combine):
+    from . import baselines
+    out = {}
+    for name, n, layers in datasets:
+        print("\nTesting dataset %s" % name)
+        out[name] = baselines.evaluate_real_data(name, n, layers, output, method, combine, data_root=data_root)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="mdcommunity_amd.cli", description=__doc__.split("\n\n")[0])
-    ap.add_argument("variant", choices=["unit", "degree", "community"])
+    ap.add_argument("variant", choices=["unit", "degree", "community", "baseline"])
     ap.add_argument("command", choices=["testSynthetic", "testReal", "train", "drawLmcc"])
     ap.add_argument("-o", "--output", required=True, help="path to output file")
     ap.add_argument("--data-root", default="../../data", help="directory holding synthetic/ and real/")
@@ -113,10 +127,20 @@ def main(argv=None):
     ap.add_argument("--types", default=",".join(SYN_TYPES))
     ap.add_argument("--dataset", action="append", default=None, help="name:N:l1,l2 (repeatable)")
     ap.add_argument("--step-ratio", type=float, default=0.0)
+    ap.add_argument("--method", choices=["hda", "ci"], default="hda", help="baseline variant: the heuristic")
+    ap.add_argument("--combine", choices=["max", "add"], default="max", help="baseline variant: the layer combine")
     a = ap.parse_args(argv)
     if a.command in ("train", "drawLmcc"):
         print("%s is not part of the MI355X inference engine (training and plotting are out of scope)" % a.command)
         return 2
+    if a.variant == "baseline":
+        if a.command != "testReal":
+            ap.error("the baseline variant has testReal only")
+        if not a.dataset:
+            ap.error("the baseline variant needs --dataset name:N:l1,l2 (the scripts' own lists name files the "
+                     "reference does not ship)")
+        test_baseline(a.output, a.data_root, [_dataset(s) for s in a.dataset], a.method, a.combine)
+        return 0
     if a.variant == "community" and a.model is None and not os.path.exists(COMMUNITY_MODEL):
         ap.error("the community variant ships no checkpoint: --model is required (%s does not exist)" % COMMUNITY_MODEL)
     if a.command == "testSynthetic":

@@ -34,6 +34,10 @@ hipError_t launch_h0(const float* w, float* tab, int dm_lo, int dm_hi, bool comm
 hipError_t launch_reset(const Params& p, hipStream_t s);
 hipError_t launch_clear(void* const* ptr, const size_t* bytes, int n, hipStream_t s);
 hipError_t set_kernel_attrs();
+bool heur_fits_lds_host(int n, int edges);
+hipError_t launch_heur(const Params& p, const float* wimg, int grid, hipStream_t s);
+int heur_pick_blocks(int n);
+hipError_t launch_heur_pick(const Params& p, long long* part, unsigned* ctr, int nb, int kind, int comb, hipStream_t s);
 }  // namespace md
 
 using namespace md;
@@ -191,6 +195,10 @@ struct md_ctx {
   DevBuf<int> pfx;       // their scratch (md_env.h pfx_words)
   HostBuf<int> h_tr;         // mapped host mirrors of tr_action [tot_n] and tr_rank [tot_n] (trace_publish)
   bool first_req = true;  // MD_FIRST_REQ=0: no speculative request at a rollout's first step
+  // baseline-heuristic picks over the HBM state (md_heuristic_rollout): per-block arg-max
+  // partials and per-graph arrival counters, allocated at the first such rollout of a batch
+  DevBuf<long long> heur_part;
+  DevBuf<unsigned> heur_ctr;
   DevBuf<unsigned long long> dfbuf;
   int df_mt = 0, df_n = 0;
   std::vector<char> df_graph;
@@ -219,7 +227,7 @@ struct md_ctx {
     covered.release(); live.release(); gscr.release(); pend.release(); tr_action.release(); tr_rank.release();
     tr_stat.release(); glist.release(); gtoff.release(); ctl.release(); tpart.release(); lab_ok.release(); gscr_team.release(); pfx.release(); bspec.release(); prank.release(); q.release(); spart.release();
     apart.release(); ybuf.release(); hbuf.release(); xbuf.release(); nbc.release(); qslot.release(); qg.release(); tr_q.release(); node_w.release(); prior.release();
-    sres.release(); qspec.release(); bars.release(); dfbuf.release();
+    sres.release(); qspec.release(); bars.release(); dfbuf.release(); heur_part.release(); heur_ctr.release();
     df_graph.clear();
     h_req.release(); h_ans.release(); h_nact.release(); h_act.release(); h_q.release(); h_chk.release();
     h_done.release(); h_gvar.release(); h_tr.release();
@@ -1574,6 +1582,158 @@ md_status md_rollout_packed(md_ctx* c, int step, int32_t* seq_packed, int32_t* l
     seq_len[g] = len;
     tot += len;
   }
+  return MD_OK;
+}
+
+namespace {
+// The LDS-resident heuristic rollout of the graphs in gl (md_heur_kernel: one workgroup per graph,
+// persistent grid), longest first.
+md_status heur_launch_lds(md_ctx* c, std::vector<int> gl, int kind, int combine) {
+  std::stable_sort(gl.begin(), gl.end(), [&](int a, int b) {
+    return (long)c->hinfo[a].e[0] + c->hinfo[a].e[1] > (long)c->hinfo[b].e[0] + c->hinfo[b].e[1];
+  });
+  for (size_t i0 = 0; i0 < gl.size(); i0 += QG_CAP) {  // (glist holds the loaded graphs; chunks only bound a launch)
+    const int ngl = (int)std::min<size_t>(QG_CAP, gl.size() - i0);
+    HIPCHK(c, hipMemcpyAsync(c->glist.p, gl.data() + i0, sizeof(int) * ngl, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ctl.p, 0, sizeof(int) * CTL_WORDS, c->stream));
+    Params p = make_params(c);
+    p.nglist = ngl;
+    p.variant = c->variant;
+    p.launch_seq = ++c->launch_seq;
+    p.run_mode = RUN_STEP;
+    p.sel_step = kind | (combine << 8);  // md_heur.h heur_kind / heur_combine
+    const int grid = std::max(1, std::min(ngl, c->cus));
+    if (trace_on())
+      std::fprintf(stderr, "md trace: ctx %p launch %u heuristic %d/%d grid %d graphs %d\n", (void*)c, p.launch_seq, kind,
+                   combine, grid, ngl);
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, launch_heur(p, c->wimg.p, grid, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    int dev_err = 0;
+    HIPCHK(c, hipMemcpyAsync(&dev_err, c->ctl.p + CTL_ERR, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_ms += ms;
+    c->last_launches += 1;
+    if (dev_err) {
+      (void)pull_vars(c);
+      return fail(c, dev_err == 1 ? MD_ETIMEOUT : MD_EINVAL, "device: %s (code %d)", err_name(dev_err), dev_err);
+    }
+  }
+  return pull_vars(c);
+}
+
+// The heuristic rollout of graphs whose state stays in HBM: one pick launch (md_heur_pick_kernel
+// queues each graph's pick as its pending action) and one environment-step launch (md_step's)
+// per removal, every graph of gl advancing together.
+md_status heur_run_hbm(md_ctx* c, const std::vector<int>& gl, int kind, int combine) {
+  // the residual degrees the pick reads are those of the last environment step: run one without
+  // actions first (it also runs a deferred s0 prune, and refreshes them after md_set_state)
+  for (int g : gl) {
+    c->hvar[g].status = ST_RUN;
+    c->hvar[g].npend = 0;
+  }
+  md_status st = push_vars(c);
+  if (st != MD_OK) return st;
+  st = launch(c, gl, RUN_STEP, 0);
+  if (st != MD_OK) return st;
+  int max_n = 1;
+  for (int g : gl) max_n = std::max(max_n, c->hinfo[g].n);
+  const int nb = heur_pick_blocks(max_n);
+  if (c->heur_ctr.n < gl.size() || c->heur_part.n < 2 * (size_t)nb * gl.size()) {
+    HIPCHK(c, c->heur_part.alloc(2 * (size_t)nb * gl.size()));
+    HIPCHK(c, c->heur_ctr.alloc(gl.size()));
+  }
+  // the arrival counters start at zero (the last block of a pick launch leaves them so; a launch
+  // that failed half-way in an earlier call may not have)
+  HIPCHK(c, hipMemsetAsync(c->heur_ctr.p, 0, sizeof(unsigned) * gl.size(), c->stream));
+  std::vector<int> act;
+  while (true) {
+    act.clear();
+    for (int g : gl)
+      if (c->hvar[g].alive[0] > 0 && c->hvar[g].alive[1] > 0) act.push_back(g);
+    if (act.empty()) break;
+    for (size_t i0 = 0; i0 < act.size(); i0 += G_CAP) {
+      const int ngl = (int)std::min<size_t>(G_CAP, act.size() - i0);
+      HIPCHK(c, hipMemcpyAsync(c->glist.p, act.data() + i0, sizeof(int) * ngl, hipMemcpyHostToDevice, c->stream));
+      Params p = make_params(c);
+      p.nglist = ngl;
+      HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+      HIPCHK(c, launch_heur_pick(p, c->heur_part.p, c->heur_ctr.p, nb, kind, combine, c->stream));
+      HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev1));
+      float ms = 0.f;
+      HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+      c->last_ms += ms;
+      c->last_launches += 1;
+    }
+    for (int g : act) {
+      c->hvar[g].status = ST_RUN;
+      c->hvar[g].npend = 1;
+    }
+    st = push_vars(c);
+    if (st != MD_OK) return st;
+    st = launch(c, act, RUN_STEP, 0);  // (a pick of -1, no live node, is the step's ERR_BADNODE)
+    if (st != MD_OK) return st;
+  }
+  // the traces of these graphs to the host mirrors md_rollout's outputs are read from
+  for (int g : gl) {
+    const GraphInfo& gi = c->hinfo[g];
+    const int len = std::min(c->hvar[g].steps, gi.n);
+    if (len <= 0) continue;
+    HIPCHK(c, hipMemcpyAsync(c->h_tr.h + gi.node_off, c->tr_action.p + gi.node_off, sizeof(int) * len, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_tr.h + c->tot_n + gi.node_off, c->tr_rank.p + gi.node_off, sizeof(int) * len, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MD_OK;
+}
+}  // namespace
+
+int md_heuristic_fits_lds(int n_nodes, int n_edges) {
+  return n_nodes > 0 && n_edges >= 0 && heur_fits_lds_host(n_nodes, n_edges) ? 1 : 0;
+}
+
+md_status md_heuristic_rollout(md_ctx* c, int kind, int combine, int32_t* seq_out, int32_t* lmcc_out, int32_t* seq_len) {
+  if (!c) return MD_EINVAL;
+  if (c->ng == 0) return fail(c, MD_ESTATE, "no graphs loaded");
+  if (kind != MD_HEUR_HDA && kind != MD_HEUR_CI) return fail(c, MD_EINVAL, "unknown heuristic kind %d", kind);
+  if (combine != MD_COMBINE_MAX && combine != MD_COMBINE_ADD) return fail(c, MD_EINVAL, "unknown layer combine %d", combine);
+  if (c->cost_mode == MD_COST_DEGREE)
+    return fail(c, MD_EINVAL, "heuristic rollouts are unit-cost only (the degree-cost baselines score differently)");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->last_ms = 0.0;
+  c->last_served = 0;
+  c->last_launches = 0;
+  // the path per graph: LDS-resident when the environment fits (MD_VARIANT bit 64: never), else
+  // the pick kernel over the HBM state.  A graph already terminal has nothing to run; after
+  // md_reset_deferred every graph runs (its first step is the s0 prune).
+  const bool pending = c->s0_pending;
+  c->s0_pending = false;
+  std::vector<int> lds, hbm;
+  for (int g = 0; g < c->ng; ++g) {
+    GraphVar& v = c->hvar[g];
+    if (!pending && (v.alive[0] == 0 || v.alive[1] == 0)) continue;
+    const GraphInfo& gi = c->hinfo[g];
+    if (heur_fits_lds_host(gi.n, gi.e[0] + gi.e[1]) && !(c->variant & 64)) lds.push_back(g);
+    else hbm.push_back(g);
+    v.status = ST_RUN;
+    v.npend = 0;
+  }
+  if (!lds.empty()) {
+    md_status st = push_vars(c);
+    if (st != MD_OK) return st;
+    st = heur_launch_lds(c, lds, kind, combine);
+    if (st != MD_OK) return st;
+  }
+  if (!hbm.empty()) {
+    const md_status st = heur_run_hbm(c, hbm, kind, combine);
+    if (st != MD_OK) return st;
+  }
+  if (seq_out) std::memcpy(seq_out, c->h_tr.h, sizeof(int) * c->tot_n);
+  if (lmcc_out) std::memcpy(lmcc_out, c->h_tr.h + c->tot_n, sizeof(int) * c->tot_n);
+  if (seq_len)
+    for (int g = 0; g < c->ng; ++g) seq_len[g] = c->hvar[g].steps;
   return MD_OK;
 }
 

@@ -168,6 +168,8 @@ struct Params {
   int sel_step;                    // step > 1: picks per prediction; dev_topk: the grid-wide step's
   int dev_topk;                    //   prediction picks its k largest Q on the device when they are
                                    //   distinct and above the rest (md_kernels.hip device_topk)
+                                   // (md_heur_kernel launches carry heuristic kind | layer combine << 8
+                                   //   in sel_step: md_heur.h)
   int* err;                        // device error word (nonzero = failure code)
   unsigned long long* prof;        // optional phase timestamps of workgroup 0 (wall clock)
   int prof_cap;                    // steps of 16 timestamp slots available in prof

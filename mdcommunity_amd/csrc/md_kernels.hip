@@ -5550,6 +5550,10 @@ __global__ void __launch_bounds__(NTHREADS, 1) md_env_kernel(Params p, const flo
   kernel_exit(kp());
 }
 
+// Baseline-heuristic rollouts (HDA / CI): their own entry points and their own instantiations of
+// the force-inlined environment pieces; nothing above reads them.
+#include "md_heur.h"
+
 // Clears up to six device ranges (bytes, multiples of 4) in one launch: the per-launch control
 // words, barrier shards and hand-off tags that would otherwise take one memset dispatch each.
 struct ClearList {
@@ -5698,6 +5702,17 @@ hipError_t launch_rollout(const Params& p, const float* wimg, int grid, hipStrea
   return hipGetLastError();
 }
 
+bool heur_fits_lds_host(int n, int et) { return phase_a_fits_lds(n, et); }
+hipError_t launch_heur(const Params& p, const float* wimg, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(md_heur_kernel, dim3(grid), dim3(NTHREADS), lds_bytes(), s, p, wimg);
+  return hipGetLastError();
+}
+int heur_pick_blocks(int n) { return std::max(1, std::min(64, (n + HEUR_PICK_THREADS - 1) / HEUR_PICK_THREADS)); }
+hipError_t launch_heur_pick(const Params& p, long long* part, unsigned* ctr, int nb, int kind, int comb, hipStream_t s) {
+  hipLaunchKernelGGL(md_heur_pick_kernel, dim3(nb, p.nglist), dim3(HEUR_PICK_THREADS), 0, s, p, part, ctr, kind, comb);
+  return hipGetLastError();
+}
+
 hipError_t launch_h0(const float* w, float* tab, int dm_lo, int dm_hi, bool community, hipStream_t s) {
   if (dm_hi < dm_lo) return hipSuccess;
   if (community)
@@ -5736,6 +5751,8 @@ hipError_t set_kernel_attrs() {
   e = hipFuncSetAttribute((const void*)md_queue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes());
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)md_wq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes());
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)md_heur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes());
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)md_env_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes());
 }
