@@ -200,6 +200,42 @@ md_status md_heuristic_rollout(md_ctx* ctx, int kind, int combine, int32_t* seq_
  * layers together) resident in LDS, 0 when it takes the HBM path (MD_VARIANT 64 aside). */
 int md_heuristic_fits_lds(int n_nodes, int n_edges);
 
+/* The reference's betweenness / closeness baselines as device rollouts (baseline/HBA/hba_add.py,
+ * hba_2max.py, baseline/HCA/hca_add.py, hca_2max.py: their adaptive critical_number, which
+ * recomputes nx.betweenness_centrality / nx.closeness_centrality of both layers before every
+ * removal; hba_2max.py's static one_pass is not built).  G_l is layer l without covered nodes and
+ * without covered or pruned edges, isolated uncovered nodes kept; L = n - covered nodes.
+ *   MD_CENT_CLOSENESS    c_l(v) = ((r - 1.0) / tot) * ((r - 1.0) / (L - 1)) with r the nodes a BFS
+ *                        from v reaches (v included) and tot the sum of their distances; 0.0 when
+ *                        tot == 0 or L <= 1.  Bit for bit networkx's value (wf_improved).
+ *   MD_CENT_BETWEENNESS  c_l(v) = scale * sum over sources s != v of the Brandes dependency
+ *                        delta_s(v), scale = 1 / ((L - 1)(L - 2)) when L > 2 (else none), all in
+ *                        double, every operation rounded on its own, in a fixed order: sigma over
+ *                        the predecessors and delta over the successors in CSR row order (the
+ *                        order a node's edges were loaded in), the sources in blocks of 8
+ *                        consecutive ids, each block summed ascending from 0.0, the block sums
+ *                        ascending from 0.0, then one multiply.  The result does not depend on
+ *                        the batch, the launch geometry or where the search arrays live.
+ * combine: MD_COMBINE_MAX max(c_0, c_1), MD_COMBINE_ADD c_0 + c_1.  The live node (layer-0 residual
+ * degree > 0) of largest combined score is removed, the smallest id among exact equals (the
+ * scripts draw among the maxima with random.choice, over isolated nodes too when every score is
+ * 0), until the state is terminal (the scripts' lastm == 1).  Start states, outputs and the state
+ * left behind as md_heuristic_rollout.  Every removal takes the centrality launches (an
+ * all-sources BFS of both layers of every graph still running) and one environment-step launch.
+ * MD_ESTATE: no graphs loaded; MD_EINVAL: unknown kind or combine, or a degree-cost context.
+ * MD_CENT_SCRATCH=1 (read by md_create) keeps the per-source search arrays in HBM scratch for
+ * every graph, as graphs too large for a workgroup's LDS have them; MD_CENT_ROUND_BLOCKS=k bounds
+ * the source blocks one launch round covers (by default the buffers' budgets do, which only
+ * large batches and graphs reach).  The results are the same. */
+enum { MD_CENT_BETWEENNESS = 0, MD_CENT_CLOSENESS = 1 };
+md_status md_centrality_rollout(md_ctx* ctx, int kind, int combine, int32_t* seq_out, int32_t* lmcc_out,
+                                int32_t* seq_len);
+
+/* The per-node scores c_0, c_1 above of the current state of every loaded graph (sum of n_nodes
+ * doubles each; either pointer may be null).  Covered and isolated nodes score 0.0.  No pick is
+ * taken and the state does not change (a prune md_reset_deferred left pending runs first). */
+md_status md_centrality_scores(md_ctx* ctx, int kind, double* layer0, double* layer1);
+
 /* Per-step diagnostics of the last md_rollout for graph g (capacity n_nodes[g] rows):
  * live nodes, alive edges in layer 0 and 1, number of nodes tied at the max, per prediction,
  * and (float) the best Q and top-2 gap.  Returns the number of predictions made. */

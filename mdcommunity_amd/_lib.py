@@ -24,6 +24,8 @@ MD_HEUR_HDA, MD_HEUR_CI = 0, 1
 MD_COMBINE_MAX, MD_COMBINE_ADD = 0, 1
 HEUR_KINDS = {"hda": MD_HEUR_HDA, "ci": MD_HEUR_CI}
 HEUR_COMBINES = {"max": MD_COMBINE_MAX, "add": MD_COMBINE_ADD}
+MD_CENT_BETWEENNESS, MD_CENT_CLOSENESS = 0, 1
+CENT_KINDS = {"betweenness": MD_CENT_BETWEENNESS, "closeness": MD_CENT_CLOSENESS}
 STATUS_NAMES = {1: "MD_EINVAL", 2: "MD_EHIP", 3: "MD_EOOM", 4: "MD_ESTATE", 5: "MD_ETIMEOUT", 6: "MD_ECALLBACK"}
 
 # Every symbol include/mdroll.h declares (checked by tests/test_abi.py).
@@ -31,7 +33,7 @@ PROF_SLOTS = 96  # MD_PROF_SLOTS in include/mdroll.h
 
 EXPORTS = ("md_create", "md_create_model", "md_set_node_prior", "md_destroy", "md_last_error", "md_set_weights", "md_load_graphs", "md_reset",
            "md_reset_deferred", "md_max_rank",
-           "md_predict", "md_step", "md_rollout", "md_rollout_packed", "md_heuristic_rollout", "md_heuristic_fits_lds", "md_rollout_trace", "md_get_state", "md_set_state",
+           "md_predict", "md_step", "md_rollout", "md_rollout_packed", "md_heuristic_rollout", "md_heuristic_fits_lds", "md_centrality_rollout", "md_centrality_scores", "md_rollout_trace", "md_get_state", "md_set_state",
            "md_set_team_size", "md_set_tie_argsort", "md_last_timing", "md_host_requests", "md_profile", "md_profile_read",
            "md_version", "md_device_count", "md_spec_stats", "md_gmm_last_error", "md_gmm_nodes", "md_gmm_links")
 
@@ -81,6 +83,8 @@ def load_library(path=LIB_PATH):
         "md_rollout_packed": (ctypes.c_int, [vp, ctypes.c_int, _i32p, _i32p, _i32p, SELECT_CB_ADDR, vp]),
         "md_heuristic_rollout": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p]),
         "md_heuristic_fits_lds": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+        "md_centrality_rollout": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p]),
+        "md_centrality_scores": (ctypes.c_int, [vp, ctypes.c_int, _f64p, _f64p]),
         "md_rollout_trace": (ctypes.c_int, [vp, ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p, _i32p]),
         "md_spec_stats": (ctypes.c_int, [vp, ctypes.c_int, _i32p, _i32p]),
         "md_get_state": (ctypes.c_int, [vp, ctypes.c_int, _u8p, _u8p, _u8p, _i32p]),
@@ -329,6 +333,42 @@ class Engine:
         off = self.node_off
         return [(seq[int(off[g]):int(off[g]) + int(ln[g])].copy(), lm[int(off[g]):int(off[g]) + int(ln[g])].copy())
                 for g in range(len(ln))]
+
+    def centrality_rollout(self, kind="betweenness", combine="max"):
+        """The reference's HBA / HCA baseline as a device rollout from the current state to terminal
+        (md_centrality_rollout): kind "betweenness" | "closeness" (or MD_CENT_*), combine "max" |
+        "add" (or MD_COMBINE_*).  Returns [(removals, LMCC sizes)] per graph, as rollout()."""
+        k = CENT_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+        cb = HEUR_COMBINES.get(combine, combine) if isinstance(combine, str) else int(combine)
+        if isinstance(k, str) or isinstance(cb, str):
+            raise ValueError(f"unknown centrality {kind!r} / combine {combine!r}")
+        if self.n_nodes is None:
+            raise MDError("MD_ESTATE: no graphs loaded")
+        tot = int(self.node_off[-1])
+        seq = np.empty(tot, np.int32)
+        lm = np.empty(tot, np.int32)
+        ln = np.zeros(len(self.n_nodes), np.int32)
+        self._check(self.lib.md_centrality_rollout(self.h, k, cb, _ptr(seq, _i32p), _ptr(lm, _i32p), _ptr(ln, _i32p)))
+        off = self.node_off
+        return [(seq[int(off[g]):int(off[g]) + int(ln[g])].copy(), lm[int(off[g]):int(off[g]) + int(ln[g])].copy())
+                for g in range(len(ln))]
+
+    def centrality_scores(self, kind="betweenness"):
+        """The per-node centrality of the current state in both residual layers
+        (md_centrality_scores): [(float64 scores of layer 0, of layer 1)] per graph.  The state is
+        left as it is."""
+        k = CENT_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+        if isinstance(k, str):
+            raise ValueError(f"unknown centrality {kind!r}")
+        if self.n_nodes is None:
+            raise MDError("MD_ESTATE: no graphs loaded")
+        tot = int(self.node_off[-1])
+        c0 = np.empty(tot, np.float64)
+        c1 = np.empty(tot, np.float64)
+        self._check(self.lib.md_centrality_scores(self.h, k, _ptr(c0, _f64p), _ptr(c1, _f64p)))
+        off = self.node_off
+        return [(c0[int(off[g]):int(off[g + 1])].copy(), c1[int(off[g]):int(off[g + 1])].copy())
+                for g in range(len(self.n_nodes))]
 
     def trace(self, g):
         n = int(self.n_nodes[g])

@@ -13,8 +13,9 @@ the smallest id).  The ``add`` scripts draw among the maxima with ``random.choic
 deterministic rule and stop of the ``max`` scripts, so its sequences are one valid outcome of
 the scripts' rule, not their seeded draw.
 
-Out of scope: HBA / HCA (betweenness, closeness), the ``_protect`` and ``_syn`` script variants,
-and the degree-cost baselines (``MultiDismantler_degree_cost/baseline`` scores differently).
+HBA / HCA (betweenness, closeness) are in ``mdcommunity_amd.baselines_centrality``.  Out of scope:
+the ``_protect`` and ``_syn`` script variants, and the degree-cost baselines
+(``MultiDismantler_degree_cost/baseline`` scores differently).
 """
 import os
 

@@ -6,8 +6,8 @@
     python -m mdcommunity_amd.cli degree testReal      --output DIR   # D/testReal.py
     python -m mdcommunity_amd.cli community testReal --output DIR --model CKPT   # CE/testReal.py
     python -m mdcommunity_amd.cli community testSynthetic --output DIR --model CKPT
-    python -m mdcommunity_amd.cli baseline testReal --method {hda,ci} --combine {max,add} -o DIR \
-        --dataset name:N:l1,l2                                        # baseline/HDA, baseline/CI scripts
+    python -m mdcommunity_amd.cli baseline testReal --method {hda,ci,hba,hca} --combine {max,add} -o DIR \
+        --dataset name:N:l1,l2                                        # baseline/HDA, CI, HBA, HCA scripts
 
 Same inputs and outputs as the reference scripts: testSynthetic reads
 ``<data-root>/synthetic/<type>/syn_<N>/adj{1,2}_<i>.npy`` and writes
@@ -18,7 +18,8 @@ Same inputs and outputs as the reference scripts: testSynthetic reads
 GPU through libmdroll.so.  The ``community`` variant is the community-enhanced model
 (CEMultiDismantler, boundary prior); no checkpoint of it is shipped, so ``--model`` is required
 unless the reference's default checkpoint path exists.  The ``baseline`` variant runs the
-reference's HDA / CI heuristics (mdcommunity_amd.baselines) on the datasets given with
+reference's HDA / CI heuristics (mdcommunity_amd.baselines) or its betweenness / closeness
+baselines HBA / HCA (mdcommunity_amd.baselines_centrality) on the datasets given with
 ``--dataset`` and writes the scripts' ``remove_nodes*`` / ``MaxCCList_Strategy_*`` files into the
 output directory; it loads no model.  Training (``train``, ``drawLmcc``) is out of scope.
 """
@@ -108,11 +109,12 @@ def test_real(variant, output, data_root, datasets, step_ratio=0.0, model=None):
 
 
 def test_baseline(output, data_root, datasets, method, combine):
-    from . import baselines
+    from . import baselines, baselines_centrality
+    mod = baselines_centrality if method in baselines_centrality.METHODS else baselines
     out = {}
     for name, n, layers in datasets:
         print("\nTesting dataset %s" % name)
-        out[name] = baselines.evaluate_real_data(name, n, layers, output, method, combine, data_root=data_root)
+        out[name] = mod.evaluate_real_data(name, n, layers, output, method, combine, data_root=data_root)
     return out
 
 
@@ -127,7 +129,7 @@ def main(argv=None):
     ap.add_argument("--types", default=",".join(SYN_TYPES))
     ap.add_argument("--dataset", action="append", default=None, help="name:N:l1,l2 (repeatable)")
     ap.add_argument("--step-ratio", type=float, default=0.0)
-    ap.add_argument("--method", choices=["hda", "ci"], default="hda", help="baseline variant: the heuristic")
+    ap.add_argument("--method", choices=["hda", "ci", "hba", "hca"], default="hda", help="baseline variant: the heuristic")
     ap.add_argument("--combine", choices=["max", "add"], default="max", help="baseline variant: the layer combine")
     a = ap.parse_args(argv)
     if a.command in ("train", "drawLmcc"):

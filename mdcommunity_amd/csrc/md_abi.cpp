@@ -38,6 +38,13 @@ bool heur_fits_lds_host(int n, int edges);
 hipError_t launch_heur(const Params& p, const float* wimg, int grid, hipStream_t s);
 int heur_pick_blocks(int n);
 hipError_t launch_heur_pick(const Params& p, long long* part, unsigned* ctr, int nb, int kind, int comb, hipStream_t s);
+bool cent_fits_lds_host(int n, int kind);
+int cent_src_block();
+long long cent_scr_wg_bytes(int n, int kind);
+hipError_t launch_cent(const Params& p, double* part, double* acc, unsigned char* scr, long long scr_wg, int max_n,
+                       int sb0, int rblocks, int kind, int tot_n, hipStream_t s);
+hipError_t launch_cent_pick(const Params& p, const double* acc, double* out, long long* part, unsigned* ctr, int nb,
+                            int kind, int comb, int tot_n, hipStream_t s);
 }  // namespace md
 
 using namespace md;
@@ -199,6 +206,14 @@ struct md_ctx {
   // partials and per-graph arrival counters, allocated at the first such rollout of a batch
   DevBuf<long long> heur_part;
   DevBuf<unsigned> heur_ctr;
+  // centrality rollouts (md_centrality_rollout / md_centrality_scores, md_cent.h), allocated at
+  // the first such call of a batch and grown on demand: betweenness block partials of a launch
+  // round, the per-node sums / scores [2][tot_n] (+ the scaled copy md_centrality_scores reads),
+  // and the HBM search arrays of graphs too large for LDS (MD_CENT_SCRATCH=1: of every graph)
+  DevBuf<double> cent_part, cent_acc;
+  DevBuf<unsigned char> cent_scr;
+  bool cent_force_scr = false;
+  int cent_round_cap = 0;  // MD_CENT_ROUND_BLOCKS: at most this many source blocks per launch round (0: the budgets decide)
   DevBuf<unsigned long long> dfbuf;
   int df_mt = 0, df_n = 0;
   std::vector<char> df_graph;
@@ -228,6 +243,7 @@ struct md_ctx {
     tr_stat.release(); glist.release(); gtoff.release(); ctl.release(); tpart.release(); lab_ok.release(); gscr_team.release(); pfx.release(); bspec.release(); prank.release(); q.release(); spart.release();
     apart.release(); ybuf.release(); hbuf.release(); xbuf.release(); nbc.release(); qslot.release(); qg.release(); tr_q.release(); node_w.release(); prior.release();
     sres.release(); qspec.release(); bars.release(); dfbuf.release(); heur_part.release(); heur_ctr.release();
+    cent_part.release(); cent_acc.release(); cent_scr.release();
     df_graph.clear();
     h_req.release(); h_ans.release(); h_nact.release(); h_act.release(); h_q.release(); h_chk.release();
     h_done.release(); h_gvar.release(); h_tr.release();
@@ -868,6 +884,8 @@ md_status md_create_model(int device, const float* weights, size_t n_floats, int
   if (const char* v = std::getenv("MD_DEVTOPK")) c->dev_topk = std::atoi(v) != 0;
   if (const char* v = std::getenv("MD_EG_APPLY")) c->eg_apply = std::atoi(v) != 0;
   if (const char* v = std::getenv("MD_FIRST_REQ")) c->first_req = std::atoi(v) != 0;
+  if (const char* v = std::getenv("MD_CENT_SCRATCH")) c->cent_force_scr = std::atoi(v) != 0;
+  if (const char* v = std::getenv("MD_CENT_ROUND_BLOCKS")) c->cent_round_cap = std::max(0, std::atoi(v));
   if (const char* v = std::getenv("MD_DF")) c->df_on = std::atoi(v) != 0;
   if (const char* v = std::getenv("MD_SPEC")) c->spec_n = std::max(0, std::min(SPEC_MAX, std::atoi(v)));
   md_status st = MD_OK;
@@ -1627,7 +1645,9 @@ md_status heur_launch_lds(md_ctx* c, std::vector<int> gl, int kind, int combine)
 // The heuristic rollout of graphs whose state stays in HBM: one pick launch (md_heur_pick_kernel
 // queues each graph's pick as its pending action) and one environment-step launch (md_step's)
 // per removal, every graph of gl advancing together.
-md_status heur_run_hbm(md_ctx* c, const std::vector<int>& gl, int kind, int combine) {
+// pick(active graphs) queues every active graph's pick; null: md_heur_pick_kernel with kind / combine.
+md_status heur_run_hbm(md_ctx* c, const std::vector<int>& gl, int kind, int combine,
+                       const std::function<md_status(const std::vector<int>&)>& pick = nullptr) {
   // the residual degrees the pick reads are those of the last environment step: run one without
   // actions first (it also runs a deferred s0 prune, and refreshes them after md_set_state)
   for (int g : gl) {
@@ -1654,7 +1674,11 @@ md_status heur_run_hbm(md_ctx* c, const std::vector<int>& gl, int kind, int comb
     for (int g : gl)
       if (c->hvar[g].alive[0] > 0 && c->hvar[g].alive[1] > 0) act.push_back(g);
     if (act.empty()) break;
-    for (size_t i0 = 0; i0 < act.size(); i0 += G_CAP) {
+    if (pick) {
+      st = pick(act);
+      if (st != MD_OK) return st;
+    }
+    for (size_t i0 = 0; !pick && i0 < act.size(); i0 += G_CAP) {
       const int ngl = (int)std::min<size_t>(G_CAP, act.size() - i0);
       HIPCHK(c, hipMemcpyAsync(c->glist.p, act.data() + i0, sizeof(int) * ngl, hipMemcpyHostToDevice, c->stream));
       Params p = make_params(c);
@@ -1734,6 +1758,143 @@ md_status md_heuristic_rollout(md_ctx* c, int kind, int combine, int32_t* seq_ou
   if (lmcc_out) std::memcpy(lmcc_out, c->h_tr.h + c->tot_n, sizeof(int) * c->tot_n);
   if (seq_len)
     for (int g = 0; g < c->ng; ++g) seq_len[g] = c->hvar[g].steps;
+  return MD_OK;
+}
+
+namespace {
+constexpr size_t CENT_PART_BUDGET = 256u << 20;   // bytes of block partials per launch round
+constexpr size_t CENT_SCR_BUDGET = 1024u << 20;   // bytes of HBM search arrays per launch round
+
+// The centrality sums of the graphs in act (non-terminal, degrees current) into cent_acc, then
+// either each graph's pick queued as its pending action (out == false) or the scaled scores of
+// every node written behind the sums (cent_acc + 2 tot_n; out == true).
+md_status cent_eval(md_ctx* c, const std::vector<int>& act, int kind, int combine, bool out) {
+  const size_t tn = c->tot_n;
+  if (c->cent_acc.n < 4 * tn) HIPCHK(c, c->cent_acc.alloc(4 * tn));
+  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+  if (kind == MD_CENT_CLOSENESS) HIPCHK(c, hipMemsetAsync(c->cent_acc.p, 0, sizeof(double) * 2 * tn, c->stream));
+  int launches = 0;
+  for (size_t i0 = 0; i0 < act.size(); i0 += G_CAP) {
+    const int ngl = (int)std::min<size_t>(G_CAP, act.size() - i0);
+    int max_n = 1;
+    for (int i = 0; i < ngl; ++i) max_n = std::max(max_n, c->hinfo[act[i0 + i]].n);
+    const bool lds = !c->cent_force_scr && cent_fits_lds_host(max_n, kind);
+    const int nsb = (max_n + cent_src_block() - 1) / cent_src_block();
+    // source blocks per launch round, bounded by the buffers a round needs
+    size_t rb = (size_t)nsb;
+    if (kind == MD_CENT_BETWEENNESS) rb = std::min(rb, CENT_PART_BUDGET / (sizeof(double) * 2 * ngl * (size_t)max_n));
+    const size_t scr_wg = lds ? 0 : (size_t)cent_scr_wg_bytes(max_n, kind);
+    if (!lds) rb = std::min(rb, CENT_SCR_BUDGET / (scr_wg * 2 * ngl));
+    if (c->cent_round_cap > 0) rb = std::min(rb, (size_t)c->cent_round_cap);
+    const int rblocks = (int)std::max<size_t>(1, rb);
+    const size_t nwg = (size_t)rblocks * 2 * ngl;
+    if (kind == MD_CENT_BETWEENNESS && c->cent_part.n < nwg * max_n) HIPCHK(c, c->cent_part.alloc(nwg * max_n));
+    if (!lds && c->cent_scr.n < nwg * scr_wg) HIPCHK(c, c->cent_scr.alloc(nwg * scr_wg));
+    const int nb = heur_pick_blocks(max_n);
+    if (c->heur_ctr.n < (size_t)ngl || c->heur_part.n < 2 * (size_t)nb * ngl) {
+      HIPCHK(c, c->heur_part.alloc(2 * (size_t)nb * ngl));
+      HIPCHK(c, c->heur_ctr.alloc(ngl));
+    }
+    HIPCHK(c, hipMemsetAsync(c->heur_ctr.p, 0, sizeof(unsigned) * ngl, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->glist.p, act.data() + i0, sizeof(int) * ngl, hipMemcpyHostToDevice, c->stream));
+    Params p = make_params(c);
+    p.nglist = ngl;
+    for (int sb0 = 0; sb0 < nsb; sb0 += rblocks) {
+      HIPCHK(c, launch_cent(p, c->cent_part.p, c->cent_acc.p, lds ? nullptr : c->cent_scr.p, (long long)scr_wg, max_n, sb0,
+                            rblocks, kind, (int)tn, c->stream));
+      launches += kind == MD_CENT_BETWEENNESS ? 2 : 1;
+    }
+    HIPCHK(c, launch_cent_pick(p, c->cent_acc.p, out ? c->cent_acc.p + 2 * tn : nullptr, c->heur_part.p, c->heur_ctr.p, nb,
+                               kind, combine, (int)tn, c->stream));
+    launches += 1;
+    if (trace_on())
+      std::fprintf(stderr, "md trace: ctx %p centrality %d/%d graphs %d max_n %d %s rounds of %d blocks\n", (void*)c, kind,
+                   combine, ngl, max_n, lds ? "lds" : "scratch", rblocks);
+  }
+  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c, hipEventSynchronize(c->ev1));
+  float ms = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  c->last_ms += ms;
+  c->last_launches += launches;
+  return MD_OK;
+}
+
+md_status cent_check(md_ctx* c, int kind) {
+  if (c->ng == 0) return fail(c, MD_ESTATE, "no graphs loaded");
+  if (kind != MD_CENT_BETWEENNESS && kind != MD_CENT_CLOSENESS) return fail(c, MD_EINVAL, "unknown centrality kind %d", kind);
+  if (c->cost_mode == MD_COST_DEGREE)
+    return fail(c, MD_EINVAL, "centrality rollouts are unit-cost only (the degree-cost baselines are out of scope)");
+  return MD_OK;
+}
+}  // namespace
+
+md_status md_centrality_rollout(md_ctx* c, int kind, int combine, int32_t* seq_out, int32_t* lmcc_out, int32_t* seq_len) {
+  if (!c) return MD_EINVAL;
+  md_status st = cent_check(c, kind);
+  if (st != MD_OK) return st;
+  if (combine != MD_COMBINE_MAX && combine != MD_COMBINE_ADD) return fail(c, MD_EINVAL, "unknown layer combine %d", combine);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->last_ms = 0.0;
+  c->last_served = 0;
+  c->last_launches = 0;
+  // every graph still running takes the loop of md_heuristic_rollout's HBM path: a first
+  // environment step without actions (deferred s0 prune, current degrees), then per removal the
+  // centrality launches and the environment step
+  const bool pending = c->s0_pending;
+  c->s0_pending = false;
+  std::vector<int> gl;
+  for (int g = 0; g < c->ng; ++g)
+    if (pending || (c->hvar[g].alive[0] > 0 && c->hvar[g].alive[1] > 0)) gl.push_back(g);
+  if (!gl.empty()) {
+    st = heur_run_hbm(c, gl, kind, combine,
+                      [&](const std::vector<int>& act) { return cent_eval(c, act, kind, combine, false); });
+    if (st != MD_OK) return st;
+  }
+  if (seq_out) std::memcpy(seq_out, c->h_tr.h, sizeof(int) * c->tot_n);
+  if (lmcc_out) std::memcpy(lmcc_out, c->h_tr.h + c->tot_n, sizeof(int) * c->tot_n);
+  if (seq_len)
+    for (int g = 0; g < c->ng; ++g) seq_len[g] = c->hvar[g].steps;
+  return MD_OK;
+}
+
+md_status md_centrality_scores(md_ctx* c, int kind, double* layer0, double* layer1) {
+  if (!c) return MD_EINVAL;
+  md_status st = cent_check(c, kind);
+  if (st != MD_OK) return st;
+  HIPCHK(c, hipSetDevice(c->device));
+  st = finish_deferred_s0(c);
+  if (st != MD_OK) return st;
+  c->last_ms = 0.0;
+  c->last_served = 0;
+  c->last_launches = 0;
+  // a terminal graph has no alive edge in either layer (the fixed point leaves equal partitions):
+  // every score is 0.0.  The others take an environment step without actions first, which leaves
+  // the state as it is and the residual degrees current (after md_set_state they are not).
+  std::vector<int> gl;
+  for (int g = 0; g < c->ng; ++g)
+    if (c->hvar[g].alive[0] > 0 && c->hvar[g].alive[1] > 0) gl.push_back(g);
+  const size_t tn = c->tot_n;
+  if (layer0) std::fill(layer0, layer0 + tn, 0.0);
+  if (layer1) std::fill(layer1, layer1 + tn, 0.0);
+  if (gl.empty()) return MD_OK;
+  for (int g : gl) {
+    c->hvar[g].status = ST_RUN;
+    c->hvar[g].npend = 0;
+  }
+  st = push_vars(c);
+  if (st != MD_OK) return st;
+  st = launch(c, gl, RUN_STEP, 0);
+  if (st != MD_OK) return st;
+  st = cent_eval(c, gl, kind, MD_COMBINE_MAX, true);
+  if (st != MD_OK) return st;
+  for (int g : gl) {
+    const GraphInfo& gi = c->hinfo[g];
+    const double* src = c->cent_acc.p + 2 * tn + gi.node_off;
+    if (layer0) HIPCHK(c, hipMemcpyAsync(layer0 + gi.node_off, src, sizeof(double) * gi.n, hipMemcpyDeviceToHost, c->stream));
+    if (layer1) HIPCHK(c, hipMemcpyAsync(layer1 + gi.node_off, src + tn, sizeof(double) * gi.n, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return MD_OK;
 }
 

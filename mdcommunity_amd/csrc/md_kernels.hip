@@ -5554,6 +5554,10 @@ __global__ void __launch_bounds__(NTHREADS, 1) md_env_kernel(Params p, const flo
 // the force-inlined environment pieces; nothing above reads them.
 #include "md_heur.h"
 
+// Betweenness / closeness centrality of the residual layers and the HBA / HCA pick: their own
+// kernels over the HBM state; nothing above reads them.
+#include "md_cent.h"
+
 // Clears up to six device ranges (bytes, multiples of 4) in one launch: the per-launch control
 // words, barrier shards and hand-off tags that would otherwise take one memset dispatch each.
 struct ClearList {
@@ -5713,6 +5717,40 @@ hipError_t launch_heur_pick(const Params& p, long long* part, unsigned* ctr, int
   return hipGetLastError();
 }
 
+bool cent_fits_lds_host(int n, int kind) { return cent_fits_lds(n, kind); }
+int cent_src_block() { return CENT_SRC_BLOCK; }
+long long cent_scr_wg_bytes(int n, int kind) {
+  return (long long)cent_npad(n) * CENT_SRC_BLOCK * cent_scr_node_bytes(kind);
+}
+// One round of the centrality search: source blocks [sb0, sb0 + rblocks) of both layers of every
+// graph of the launch list; betweenness folds the round's block partials into acc afterwards.
+hipError_t launch_cent(const Params& p, double* part, double* acc, unsigned char* scr, long long scr_wg, int max_n,
+                       int sb0, int rblocks, int kind, int tot_n, hipStream_t s) {
+  CentArgs a;
+  a.part = part;
+  a.acc = acc;
+  a.scr = scr;
+  a.scr_wg = scr_wg;
+  a.stride = max_n;
+  a.sb0 = sb0;
+  a.kind = kind;
+  a.tot_n = tot_n;
+  const int lds = scr != nullptr ? 0 : cent_npad(max_n) * CENT_SRC_BLOCK * cent_lds_node_bytes(kind);
+  hipLaunchKernelGGL(md_cent_kernel, dim3(rblocks, 2, p.nglist), dim3(CENT_THREADS), lds, s, p, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || kind != CENT_BETW) return e;
+  hipLaunchKernelGGL(md_cent_acc_kernel, dim3((max_n + CENT_PICK_THREADS - 1) / CENT_PICK_THREADS, 2, p.nglist),
+                     dim3(CENT_PICK_THREADS), 0, s, p, a, rblocks);
+  return hipGetLastError();
+}
+// out == null: queue each graph's pick (nb blocks per graph, as launch_heur_pick); else write the scores.
+hipError_t launch_cent_pick(const Params& p, const double* acc, double* out, long long* part, unsigned* ctr, int nb,
+                            int kind, int comb, int tot_n, hipStream_t s) {
+  hipLaunchKernelGGL(md_cent_pick_kernel, dim3(nb, p.nglist), dim3(CENT_PICK_THREADS), 0, s, p, acc, out, part, ctr, kind,
+                     comb, tot_n);
+  return hipGetLastError();
+}
+
 hipError_t launch_h0(const float* w, float* tab, int dm_lo, int dm_hi, bool community, hipStream_t s) {
   if (dm_hi < dm_lo) return hipSuccess;
   if (community)
@@ -5753,6 +5791,8 @@ hipError_t set_kernel_attrs() {
   e = hipFuncSetAttribute((const void*)md_wq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes());
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)md_heur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes());
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)md_cent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CENT_LDS_BYTES);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)md_env_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes());
 }
